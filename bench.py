@@ -22,10 +22,16 @@ per launch) and reports the same GPU with 3 steps in flight as
 ``pipelined``, the like-for-like base for an N > 1 line.  Fixed total work
 per step -> "scaling": "strong".
 
-The JSON line also carries
+A plain run sets up, warms up, times ``--steps`` steps and prints the JSON
+line: the headline keys and
   roofline      algorithmic bytes of the DFS kernel per launch
                 (B_src = 4(V+1) + 4E + 4(V-1) + 8V per source)
-                / its mean duration from HIP events on its stream, vs 8 TB/s;
+                / its mean duration from HIP events on its stream (inside the
+                timed steps), vs 8 TB/s.
+``--dump-outputs DIR`` writes the tables of the last timed step as
+DIR/<name>.npy.  ``--full`` adds every measurement that takes runs of its own
+(single-step latency, steps in flight, the N > 1 blocks, host boundary,
+materialised flows, the drop-in) and the CPU baselines:
   cpu_baseline  the oracle's per-source C restatement on the host cores
                 (rank 0, N = 1), same workload;
   cpu_reference_path  the per-pair Python restatement of find_route (the
@@ -82,7 +88,17 @@ def parse():
     ap.add_argument("--event-every", type=int, default=10,
                     help="bracket every k-th timed launch with HIP events (kernel time; "
                          "the events themselves cost a few us per step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, each in runs of its "
+                         "own: the CPU baselines, single-step latency, rates by steps in "
+                         "flight, the host boundary, materialised flows, the drop-in and the "
+                         "N > 1 blocks (other assembly form, single process, N = 1 base)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step "
+                         "computed as DIR/<name>.npy (float64; a fixed seeded sample of an "
+                         "array when all of them would pass 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: without the CPU baselines")
     ap.add_argument("--no-flows", action="store_true",
                     help="dfs mode: skip the materialised flow-entry rate of every host pair")
     ap.add_argument("--cpu-budget-s", type=float, default=20.0,
@@ -107,7 +123,36 @@ def parse():
                     help="launcher rehearsal on CPU: the N ranks form a gloo group, shard "
                          "the sources and assemble them, and rank 0 prints the line's "
                          "multi-rank keys -- no GPU call, no kernel (tests only)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode == "matflows":
+        ap.error("--dump-outputs: --mode matflows keeps no output (one reused chunk buffer)")
+    return args
+
+
+DUMP_BUDGET = 48 << 20         # bytes of float64 over all dumped arrays (limit: 64 MB)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: `arrays` ({name: device tensor}, what the last timed
+    step left for its caller) as directory/<name>.npy in float64 (exact for
+    every integer table here).  An equal share of DUMP_BUDGET per array; an
+    array over its share is written as a fixed sample -- the elements at
+    seeded flat indices, the same from run to run -- with the indices beside
+    it as <name>.index.npy."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET // 8 // max(1, len(arrays))
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), share // 2))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            np.save(os.path.join(directory, name + ".index.npy"), idx.astype(np.float64))
+            a = flat.cpu().numpy()
+        else:
+            a = t.cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a.astype(np.float64))
 
 
 def _traffic(key):
@@ -529,6 +574,8 @@ def main_flows(args, world, rank, local, dev):
         elapsed = float(t.item())
     ms = elapsed / args.steps * 1e3
     kern_ms = float(np.mean(kms))
+    if args.dump_outputs and rank == 0:     # this rank's share of the pairs
+        dump_outputs(args.dump_outputs, {"offsets": off, "switch": sw, "port": hpo})
     # expansion: per entry parent + port read (8 B) and (switch, port)
     # written (8 B); per pair row/dst/last_port (12 B) + offsets pair (16 B)
     bytes_launch = 16 * total + 28 * n
@@ -604,6 +651,8 @@ def main_ecmp(args, world, rank, local, dev):
         elapsed = float(t.item())
     ms = elapsed / args.steps * 1e3
     kern_ms = float(np.mean(kms))
+    if args.dump_outputs and rank == 0:     # this rank's share of the destinations
+        dump_outputs(args.dump_outputs, {"paths": paths[:hi - lo]})
     # per destination: dist row read (2V), CSR read (4(V+1) + 4E), counts written (8V)
     bytes_launch = (hi - lo) * (2 * V + 4 * (V + 1) + 4 * csr.E + 8 * V)
     achieved = bytes_launch / (kern_ms / 1e3) / 1e9
@@ -659,6 +708,8 @@ def main_apsp(args, world, rank, local, dev):
     ctx.synchronize()
     ms = (time.perf_counter() - t0) / args.steps * 1e3
     kern_ms = float(np.mean(kms))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"dist": d})
     passes = ctx.last_launches()            # squaring passes of one APSP call
     sweeps = ctx.last_sweeps()              # Bellman-Ford sweeps (apsp_relax8_kernel)
     # algorithmic: one add + one min per (i, j, k) per squaring pass over the
@@ -975,7 +1026,8 @@ def main_rehearse(args, world, rank):
     else:
         ok = bool(np.array_equal(D.unpad(out.view(-1), len(srcs)).numpy(), srcs))
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:   # as the N > 1 line: rank 0, after the steps
+    # as the N > 1 line: --full, rank 0, after the steps
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(fabric, fabric.csr(), srcs, counts, fabric.n_hosts,
                            args.cpu_budget_s)[0]
     dist.barrier()
@@ -1056,7 +1108,8 @@ def main():
     if args.rehearse:
         sys.exit(main_rehearse(args, world, rank) if world > 1 else 0)
     ref_mp = None
-    if world == 1 and args.mode == "dfs" and not args.no_cpu_baseline:
+    cpu_lines = args.full and not args.no_cpu_baseline and args.mode == "dfs"
+    if world == 1 and cpu_lines:
         # forks: must run before the first GPU call of this process (and so
         # before the device count below, which may initialise HIP when
         # torch cannot count through amdsmi)
@@ -1247,6 +1300,17 @@ def main():
     routes = float(counts.sum()) * float(H)      # every host pair of these sources
     value = routes / (ms_per_step / 1e3)
 
+    if args.dump_outputs and rank == 0:
+        # the table set of the last timed step, as its caller holds it: the
+        # assembled tables at N > 1 (this rank's own rows when nothing is
+        # assembled), without the padding rows
+        k = (counter[0] - 1) % nbuf
+        last = gathered[k] if world > 1 and args.assemble != "none" else bufs[k]
+        names = ("tree",) if packed else \
+            (("parent", "port") if args.mode == "dfs" else ("dist", "nh", "nh_port"))
+        rows = S if last is gathered[k] else hi - lo
+        dump_outputs(args.dump_outputs, {n: t[:rows] for n, t in zip(names, last)})
+
     def single_step_ms():
         """ONE step alone -- launched, assembled (N > 1) and synchronized: the
         latency a controller waits for one fresh table set.  Median over a
@@ -1290,21 +1354,27 @@ def main():
         return {"steps_in_flight": k, "ms_per_step": ms, "value": routes / (ms / 1e3),
                 "steps": reps}
 
-    single_ms = None if args.profile else single_step_ms()
+    # --full: the measurements beside the headline, each in runs of its own
+    # (--profile: none of them, so that a trace holds the warmup + timed steps)
+    extras = args.full and not args.profile
+    single_ms = single_step_ms() if extras else None
     by_inflight = {str(inflight): {"steps_in_flight": inflight, "ms_per_step": ms_per_step,
                                    "value": value, "steps": args.steps, "headline": True}}
-    if inflight > 1 and not args.profile:     # the same ranks, one step at a time
+    if inflight > 1 and extras:               # the same ranks, one step at a time
         by_inflight["1"] = rate_at(1, max(args.steps // 2, 10))
     pipelined = None
     set_bytes = sum(t.numel() * t.element_size() for t in bufs[0])
-    if world == 1 and inflight == 1 and args.inflight == 0 and 3 * set_bytes <= (4 << 30) \
-            and ms_per_step <= 10.0:      # small steps only: 3 more table sets, 30+ steps
+    if args.full and world == 1 and inflight == 1 and args.inflight == 0 and \
+            3 * set_bytes <= (4 << 30) and ms_per_step <= 10.0:
+        # small steps only: 3 more table sets, 30+ steps
         pipelined = pipelined_rate(local, dev, csr, t_src, per, tables, slots, packed,
                                    args.mode, routes, max(args.steps, 30))
         by_inflight["3"] = {k: pipelined[k] for k in ("steps_in_flight", "ms_per_step",
                                                       "value", "steps")}
     multi = None
-    if world > 1:
+    if world > 1 and not args.full:
+        multi = {"assembly_check": assembly_check}
+    elif world > 1:
         multi = multi_gpu_extras(args, world, rank, local, dev, csr, srcs, per, packed, slots,
                                  kern_ms, ms_per_step, routes, step, drain, bufs, gathered,
                                  assemble, assembly_check)
@@ -1395,7 +1465,7 @@ def main():
         out["multi_gpu"] = multi
         out["config"]["assemble"] = args.assemble
         out["config"]["assemble_reason"] = ASSEMBLE_REASON[args.assemble]
-    if rank == 0 and world == 1 and args.mode == "dfs" and not args.profile and \
+    if rank == 0 and world == 1 and args.mode == "dfs" and extras and \
             float(S) * V * (4 if packed else 8) <= 4e9:
         # the drop-in's host-buffer boundary: sources in, tables out over PCIe
         # (skipped where the host copy of the tables would exceed 4 GB)
@@ -1418,7 +1488,7 @@ def main():
     # fat-trees only: their default routes are ~70 entries; a torus or
     # Jellyfish all-pairs fdb set (~2,400-5,600 entries per pair) is TBs
     if rank == 0 and world == 1 and args.mode == "dfs" and not args.max_sources and \
-            not args.no_flows and not args.profile and not args.all_vertices and \
+            not args.no_flows and extras and not args.all_vertices and \
             args.fabric.startswith("fat_tree"):
         # the form the drop-in uses: one u32 word (switch | port << 16) per
         # entry, 4 B; the two int32 arrays (8 B per entry) beside it
@@ -1426,12 +1496,12 @@ def main():
                                                        packed=True)
         out["materialised_flows_int32"] = materialised_flows(ctx, dev, stream, csr, fabric, srcs)
     if rank == 0 and world == 1 and args.mode == "dfs" and not args.max_sources and \
-            not args.no_flows and not args.profile and not args.all_vertices and \
+            not args.no_flows and extras and not args.all_vertices and \
             args.fabric.startswith("fat_tree"):
         out["dropin"] = dropin_block(fabric)
-    if world > 1 and not args.no_cpu_baseline and args.mode == "dfs":
+    if world > 1 and cpu_lines:
         dist.barrier()         # the GPU work of every rank is done: rank 0 alone on the host
-    if rank == 0 and not args.no_cpu_baseline and args.mode == "dfs":
+    if rank == 0 and cpu_lines:
         # N > 1 too (north_star: the host-CPU baseline "in the same run"):
         # pthreads and plain loops, no fork, after every rank's timed work
         base, ref, ref_pred = cpu_baseline(fabric, csr, srcs, counts, H, args.cpu_budget_s)
@@ -1443,7 +1513,7 @@ def main():
         if ref_mp is not None:
             out["cpu_reference_path_all_cores"] = ref_mp
         out["gpu_over_cpu"] = value / base["value"]
-    if world > 1 and not args.no_cpu_baseline and args.mode == "dfs":
+    if world > 1 and cpu_lines:
         dist.barrier()
     if rank == 0:
         print(json.dumps(out), flush=True)

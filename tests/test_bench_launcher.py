@@ -32,7 +32,7 @@ def _run(args, env, timeout=300):
 
 @pytest.mark.parametrize("n,form", [(2, "root"), (3, "root"), (2, "all"), (2, "none")])
 def test_bench_gpus_n_launches_n_ranks(n, form):
-    r = _run(["--gpus", str(n), "--rehearse", "--steps", "2", "--assemble", form,
+    r = _run(["--gpus", str(n), "--rehearse", "--full", "--steps", "2", "--assemble", form,
               "--cpu-budget-s", "2"], _env())
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

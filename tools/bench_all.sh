@@ -3,7 +3,7 @@
 OUT=${1:-gpurun_out/bench_all.jsonl}
 mkdir -p "$(dirname "$OUT")"; : > "$OUT"
 run() {  # fabric mode steps warmup extra...
-  timeout -k 10 ${TMO:-300} python bench.py --fabric "$1" --mode "$2" --steps "$3" --warmup "$4" "${@:5}" >> "$OUT" 2> "$OUT.$1.$2.err"
+  timeout -k 10 ${TMO:-300} python bench.py --full --fabric "$1" --mode "$2" --steps "$3" --warmup "$4" "${@:5}" >> "$OUT" 2> "$OUT.$1.$2.err"
   rc=$?; echo "$1 $2 rc=$rc"; case $rc in 124|134|137|139) exit $rc;; esac
 }
 run mock dfs 50 5

@@ -18,9 +18,9 @@ rc=$?; echo "pytest rc=$rc"; tail -4 "$OUT/pytest_gpu.log"; fatal $rc pytest
 timeout -k 10 300 python -c 'import __graft_entry__ as g; g.smoke()' > "$OUT/smoke.log" 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -2 "$OUT/smoke.log"; fatal $rc smoke
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; echo "bench rc=$rc"; cat "$OUT/bench.json"; fatal $rc bench
-timeout -k 10 300 python bench.py --mode shortest --steps 10 --warmup 2 --no-cpu-baseline \
+timeout -k 10 300 python bench.py --full --mode shortest --steps 10 --warmup 2 --no-cpu-baseline \
   > "$OUT/bench_shortest.json" 2> "$OUT/bench_shortest.err"
 rc=$?; echo "bench shortest rc=$rc"; cat "$OUT/bench_shortest.json"; fatal $rc bench_shortest
 if [ -f sdn-mpi-router_amd/sdnmpi_amd/libsdnroute_stamps.so ]; then

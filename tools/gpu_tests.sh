@@ -9,7 +9,7 @@ rc=$?; echo "pytest rc=$rc"; tail -25 "$OUT/pytest.log"
 case $rc in 124|134|137|139) exit $rc;; esac
 [ $rc -ne 0 ] && exit $rc
 if [ -n "$BENCH" ]; then
-  timeout -k 10 300 python bench.py $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 300 python bench.py --full $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err"
   rc=$?; echo "bench rc=$rc"; cat "$OUT/bench.json"; tail -3 "$OUT/bench.err"
 fi
 exit $rc
