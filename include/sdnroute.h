@@ -47,6 +47,8 @@ extern "C" {
                                  ones (same pointers, same contents) of the
                                  previous expansion on this context -- its
                                  derived walk tables are reused */
+#define SDNR_LOADS_TO_ROOT 0x8u /* sdnr_link_loads: rows are per-destination
+                                 next-hop rows (edges point toward the root) */
 
 #define SDNR_UNREACHED (-1)
 #define SDNR_DIST_INF  0xFFFFu
@@ -158,7 +160,7 @@ int sdnr_dfs_tables_slots(sdnr_ctx *ctx, const int32_t *src, int32_t nsrc,
  * pointers only (flags must hold SDNR_DEVICE_PTRS); asynchronous on the
  * context stream.  The route cache of the Python TopologyDB keeps its rows
  * in these layouts (a third of the int32 tables' bytes). */
-#define SDNR_TREE_INT32  0   /* int32 parents (sdnr_dfs_rows_affected only) */
+#define SDNR_TREE_INT32  0   /* int32 parents (sdnr_dfs_rows_affected, sdnr_link_loads) */
 #define SDNR_TREE_PORT16 1
 #define SDNR_TREE_SLOT   2
 int sdnr_tree_pack(sdnr_ctx *ctx, const int32_t *parent, const int32_t *port,
@@ -277,6 +279,41 @@ int sdnr_route_expand_packed(sdnr_ctx *ctx, const int32_t *parent, const int32_t
                              int32_t nrows, const int32_t *rows, const int32_t *dsts,
                              const int32_t *last_port, int32_t npairs, const int64_t *offsets,
                              uint32_t *entries, uint32_t flags);
+
+/* Per-link traffic loads of a routed traffic matrix: how much of a demand
+ * crosses each link when every pair takes the controller's route -- what the
+ * flow entries of Router._add_flows_for_path (reference sdnmpi/router.py:
+ * 83-104, one entry per switch of the route) make the ports carry, and what
+ * the real controller observes per port in sdnmpi/monitor.py.  No entry is
+ * built: per tree row the load of link parent(v) -> v is the demand destined
+ * into v's subtree (ancestor doubling, O(V log depth) per row whatever the
+ * number of pairs).
+ *   tree      [nrows][V] rows: default-route trees in layout SDNR_TREE_INT32
+ *             (int32 parents, sdnr_dfs_tables), SDNR_TREE_PORT16 or
+ *             SDNR_TREE_SLOT (sdnr_dfs_tables_tree), row r = one source's tree;
+ *   pair_off  [nrows + 1] int64: the pairs of row r are dsts[pair_off[r] ..
+ *             pair_off[r+1]) (destination switches, dense ids) with weight[]
+ *             (u64, e.g. bytes) at the same indices; weight NULL: all 1;
+ *   load      [E] u64 in the uploaded CSR's edge order.  The call ADDS into
+ *             load (the caller zeroes it; row chunks of one batch sum up).
+ * Per row, load[e(parent(v) -> v)] += sum of the weights of the row's pairs
+ * whose destination lies in the subtree of v.  Repeated pairs add; a
+ * destination outside [0, V) or unreached in its row contributes nothing;
+ * sums are u64 and wrap (bit-exact, order-independent).
+ * With SDNR_LOADS_TO_ROOT the rows are per-destination next-hop rows
+ * (sdnr_shortest_tables' nh, layout SDNR_TREE_INT32 only; root and unreached
+ * vertices hold -1), dsts[] name the flows' SOURCE switches and the link is
+ * v -> nh[v]: the loads of routes[0] of find_route(multiple=True).
+ * A vertex has no ancestor when its int32 parent is < 0 or itself.
+ * Device pointers only (flags must hold SDNR_DEVICE_PTRS); asynchronous on
+ * the context stream (pair_off[0] and pair_off[nrows] are read back first:
+ * not monotone is SDNR_ERR_INVAL); on a multi-device context it runs on the
+ * primary device.  nrows == 0 or no pairs: SDNR_OK, nothing touched.  A row
+ * that is not a tree of the graph is reported by sdnr_synchronize as
+ * SDNR_ERR_INVAL (the rounds are bounded; that row adds nothing). */
+int sdnr_link_loads(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nrows,
+                    const int64_t *pair_off, const int32_t *dsts, const uint64_t *weight,
+                    uint64_t *load, uint32_t flags);
 
 /* Flood ports (TopologyManager._is_edge_port / _do_broadcast, reference
  * sdnmpi/topology.py:150-177): is_edge[i] = 1 iff ports[i] is neither end of

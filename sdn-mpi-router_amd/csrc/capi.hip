@@ -51,6 +51,11 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_dfs_rows_affected: a tree row is not a tree "
                              "(a parent chain longer than V, or a reached vertex without a "
                              "reached parent)");
+        if (h & kErrLoadsTree)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: a row is not a tree of the "
+                             "uploaded graph (an ancestor chain longer than V, a parent that is "
+                             "no vertex, a tree link the graph lacks) or pair_off is not "
+                             "monotone: loads invalid");
         if (h & kErrLastPort)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_route_expand_packed: a last port outside "
                              "[0, 0xFFFF] (u32 entries hold 16-bit ports): entries invalid");
@@ -1092,6 +1097,47 @@ int sdnr_dfs_rows_affected(sdnr_ctx *ctx, const uint32_t *tree, const void *dept
     ctx->timed = (flags & SDNR_TIMING) != 0;
     return sdnr_launch_dfs_rows_affected(ctx, tree, depth, layout, depth_bytes, nrows, row_src,
                                          links, nremoved, nadded, affected);
+}
+
+int sdnr_link_loads(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nrows,
+                    const int64_t *pair_off, const int32_t *dsts, const uint64_t *weight,
+                    uint64_t *load, uint32_t flags)
+{
+    CHECK_CTX(ctx);
+    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_link_loads: no graph uploaded");
+    if (!(flags & SDNR_DEVICE_PTRS))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: device pointers only");
+    if (nrows < 0) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: negative count");
+    if (layout != SDNR_TREE_INT32 && layout != SDNR_TREE_PORT16 && layout != SDNR_TREE_SLOT)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: layout %d", layout);
+    const bool to_root = (flags & SDNR_LOADS_TO_ROOT) != 0;
+    if (to_root && layout != SDNR_TREE_INT32)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: SDNR_LOADS_TO_ROOT takes int32 "
+                         "next-hop rows (layout %d)", layout);
+    if (layout == SDNR_TREE_PORT16 && ctx->V > 0xFFFF)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: port16 needs V <= 65535 (V=%d)",
+                         ctx->V);
+    if (layout == SDNR_TREE_SLOT && ctx->V > (1 << 26) - 1)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: slots need V < 2^26 (V=%d)", ctx->V);
+    if (nrows == 0) return SDNR_OK;
+    if (!tree || !pair_off || !load)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: null pointer");
+    SDNR_HIP(hipSetDevice(ctx->device));
+    // the bounds of the pair list: pair_off[0], pair_off[nrows] (two int64)
+    int w[4];
+    int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off), 2, w);
+    if (!rc) rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off + nrows), 2, w + 2);
+    if (rc) return rc;
+    const int64_t lo = (int64_t)(((uint64_t)(uint32_t)w[1] << 32) | (uint32_t)w[0]);
+    const int64_t hi = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
+    if (lo < 0 || hi < lo)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: pair_off not monotone (pair_off[0]="
+                         "%lld, pair_off[%d]=%lld)", (long long)lo, nrows, (long long)hi);
+    if (hi == lo || ctx->V == 0) return SDNR_OK;
+    if (!dsts) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: null pointer");
+    ctx->timed = (flags & SDNR_TIMING) != 0;
+    return sdnr_launch_link_loads(ctx, tree, layout, to_root, nrows, pair_off, lo, hi, dsts,
+                                  weight, load);
 }
 
 int sdnr_shortest_tables(sdnr_ctx *ctx, const int32_t *dst, int32_t ndst, uint16_t *dist,

@@ -164,6 +164,13 @@ constexpr int kErrLastPort = 256;   // sdnr_route_expand_packed: a last port out
 constexpr int kErrTreeClimb = 512;  // sdnr_dfs_rows_affected: a tree climb outran V steps
 constexpr int kErrScan = 1024;      // sdnr_route_offsets: a look-back wait ran out
 constexpr int kErrSeg = 2048;       // route expansion: a walker / storer hand-off wait ran out
+constexpr int kErrLoadsTree = 4096; // sdnr_link_loads: a row is not a tree of the graph / bad offsets
+
+// sdnr_link_loads keeps a row's sums and ancestors in LDS (20 bytes per
+// vertex: 160,000 of the CU's 163,840) up to this V, else in global scratch
+// (24 bytes per vertex and workgroup, at most kLoadsScratchBytes in all)
+constexpr int kLoadsLdsMaxV = 8000;
+constexpr size_t kLoadsScratchBytes = (size_t)1 << 30;
 
 // error plumbing (capi.hip)
 int sdnr_fail(int code, const char *fmt, ...);
@@ -226,5 +233,11 @@ int sdnr_launch_dfs_rows_affected(sdnr_ctx *ctx, const uint32_t *d_tree, const v
                                   int32_t layout, int32_t depth_bytes, int32_t nrows,
                                   const int32_t *d_row_src, const int32_t *d_links, int32_t nrm,
                                   int32_t nadd, uint8_t *d_affected);
+// per-link loads of a demand routed over tree rows (loads.hip); pair_lo /
+// pair_hi = pair_off[0] / pair_off[nrows], the bounds of the pair list
+int sdnr_launch_link_loads(sdnr_ctx *ctx, const void *d_tree, int32_t layout, bool to_root,
+                           int32_t nrows, const int64_t *d_pair_off, int64_t pair_lo,
+                           int64_t pair_hi, const int32_t *d_dsts, const uint64_t *d_weight,
+                           uint64_t *d_load);
 int sdnr_launch_edge_ports(sdnr_ctx *ctx, const uint64_t *d_ends, int32_t nends,
                            const uint64_t *d_ports, int32_t nports, uint8_t *d_is_edge);

@@ -25,6 +25,7 @@ _LIB_NAME = "libsdnroute.so"
 DEVICE_PTRS = 0x1
 TIMING = 0x2
 SAME_TABLES = 0x4        # route expansion: the previous call's parent / port tables
+LOADS_TO_ROOT = 0x8      # sdnr_link_loads: per-destination next-hop rows
 UNREACHED = -1
 DIST_INF = 0xFFFF
 TREE_NONE = 0xFFFFFFFF
@@ -42,7 +43,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_apsp", "sdnr_route_offsets", "sdnr_route_expand", "sdnr_ecmp_counts",
     "sdnr_ecmp_routes",
     "sdnr_last_kernel_ms", "sdnr_last_kernel", "sdnr_last_launches", "sdnr_last_sweeps",
-    "sdnr_edge_ports", "sdnr_dfs_rows_affected",
+    "sdnr_edge_ports", "sdnr_dfs_rows_affected", "sdnr_link_loads",
 )
 
 
@@ -98,6 +99,7 @@ def _bind(L):
         "sdnr_last_sweeps": ([vp, ctypes.POINTER(i32)], c_int),
         "sdnr_edge_ports": ([vp, vp, i32, vp, i32, vp, u32], c_int),
         "sdnr_dfs_rows_affected": ([vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, u32], c_int),
+        "sdnr_link_loads": ([vp, vp, i32, i32, vp, vp, vp, vp, u32], c_int),
     }
     # an A/B build named by SDNROUTE_LIB may predate some entry points: those
     # stay unbound (calling one raises AttributeError); the in-tree library
@@ -415,6 +417,20 @@ class Context(object):
             int(depth_bytes), int(nrows), ctypes.c_void_p(row_src_ptr),
             ctypes.c_void_p(links_ptr) if links_ptr else None, int(nremoved), int(nadded),
             ctypes.c_void_p(affected_ptr), flags))
+
+    def link_loads_device(self, tree_ptr, layout, nrows, pair_off_ptr, dsts_ptr, weight_ptr,
+                          load_ptr, to_root=False, timing=False):
+        """Add the per-link loads of a demand routed over [nrows][V] tree rows
+        into ``load`` (u64 [E], CSR edge order; the caller zeroes it):
+        sdnr_link_loads, device pointers, asynchronous.  ``weight_ptr`` 0:
+        every pair weighs 1; ``to_root``: next-hop rows (SDNR_LOADS_TO_ROOT)."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_TO_ROOT if to_root else 0)
+        _check(self._lib.sdnr_link_loads(
+            self._h, ctypes.c_void_p(tree_ptr) if tree_ptr else None, int(layout), int(nrows),
+            ctypes.c_void_p(pair_off_ptr) if pair_off_ptr else None,
+            ctypes.c_void_p(dsts_ptr) if dsts_ptr else None,
+            ctypes.c_void_p(weight_ptr) if weight_ptr else None,
+            ctypes.c_void_p(load_ptr) if load_ptr else None, flags))
 
     def apsp(self):
         dist = np.empty((self.V, self.V), np.uint16)

@@ -41,7 +41,7 @@ from .graph import empty_csr
 
 __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "shortest_paths_lex", "count_shortest_paths", "ECMP_LIMIT", "DEFAULT_TABLE_BUDGET", "tree_layout", "dfs_row_bytes",
-           "sp_row_bytes"]
+           "sp_row_bytes", "link_loads_host"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -244,6 +244,90 @@ def pack_host_tree(parent, port, csr, layout):
         slot = np.where(p == v, 63, slot)
         t = np.where(ok, p | (slot << 26), 0xFFFFFFFF)
     return (t & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def _pairs_by_row(rows, nrows):
+    """(order, off): a stable order of the pairs by row and the int64
+    [nrows + 1] offsets of each row's pairs in it (sdnr_link_loads' pair_off)."""
+    if rows.shape[0] < 2 or bool((rows[1:] >= rows[:-1]).all()):
+        order = slice(None)                              # already grouped by row
+    else:
+        order = np.argsort(rows, kind="stable")
+    off = np.zeros(nrows + 1, np.int64)
+    np.cumsum(np.bincount(rows, minlength=nrows), out=off[1:])
+    return order, off
+
+
+def _gather(a, r, c):
+    """a[r[i], c[i]] of a [k, V] table (numpy or device tensor) as numpy."""
+    if _is_np(a):
+        return a[r, c]
+    t = _torch()
+    return a[t.as_tensor(r, dtype=t.int64, device=a.device),
+             t.as_tensor(c, dtype=t.int64, device=a.device)].cpu().numpy()
+
+
+def link_loads_host(csr, tree, layout, rows, dsts, weights=None, to_root=False):
+    """numpy restatement of sdnr_link_loads (the CPU tests' engine double and
+    an independent check of loads.hip): uint64 [E] loads of pairs (row
+    ``rows[i]`` of ``tree``, switch ``dsts[i]``, weight ``weights[i]`` or 1).
+
+    Deliberately not the kernel's algorithm: the tree depths are found first,
+    then the demand is pushed to the parents one level at a time, deepest
+    level first (``np.add.at``), so every vertex is final before it is
+    passed on; the load of link parent(v) -> v (``to_root``: v -> parent) is
+    what v passes on.  u64 sums wrap, as on the device."""
+    V, E = int(csr.V), int(csr.E)
+    load = np.zeros(E, np.uint64)
+    rows = np.asarray(rows, np.int64)
+    dsts = np.asarray(dsts, np.int64)
+    if rows.size == 0 or E == 0:
+        return load
+    w = np.ones(rows.shape[0], np.uint64) if weights is None else np.asarray(weights, np.uint64)
+    used, rix = np.unique(rows, return_inverse=True)
+    words = np.asarray(tree)[used]
+    if layout == INT32:
+        par = words.astype(np.int64)
+    else:
+        par = tree_parent(words, layout)
+    n = par.shape[0]
+    vid = np.broadcast_to(np.arange(V, dtype=np.int64), par.shape)
+    par = np.where((par < 0) | (par == vid), -1, par)      # no ancestor: root / unreached
+    if (par >= V).any():
+        raise ValueError("link_loads_host: a parent that is no vertex")
+    # depth = number of ancestors, by pointer jumping
+    depth = (par >= 0).astype(np.int64)
+    jump = par.copy()
+    for _ in range(max(1, V).bit_length() + 1):
+        ok = jump >= 0
+        if not ok.any():
+            break
+        jc = np.where(ok, jump, 0)
+        depth = depth + np.where(ok, np.take_along_axis(depth, jc, 1), 0)
+        jump = np.where(ok, np.take_along_axis(jump, jc, 1), -1)
+    else:
+        raise ValueError("link_loads_host: a row is not a tree")
+    acc = np.zeros((n, V), np.uint64)
+    ok = (dsts >= 0) & (dsts < V)
+    np.add.at(acc, (rix[ok], dsts[ok]), w[ok])
+    flat = np.argsort(depth, axis=None, kind="stable")
+    cnt = np.bincount(depth.ravel())
+    ends = np.cumsum(cnt)
+    for lv in range(cnt.shape[0] - 1, 0, -1):              # deepest level first
+        idx = flat[ends[lv] - cnt[lv]:ends[lv]]
+        r, v = idx // V, idx % V
+        np.add.at(acc, (r, par[r, v]), acc[r, v])
+    r, v = np.nonzero((par >= 0) & (acc != 0))
+    if r.size == 0:
+        return load
+    p = par[r, v]
+    keys, _ = _edge_keys_host(csr)
+    k = (v * V + p) if to_root else (p * V + v)
+    e = np.minimum(np.searchsorted(keys, k), E - 1)
+    if not np.array_equal(keys[e], k):
+        raise ValueError("link_loads_host: a tree link the graph does not have")
+    np.add.at(load, e, acc[r, v])
+    return load
 
 
 class RouteEngine(object):
@@ -492,6 +576,47 @@ class RouteEngine(object):
                                           tl.data_ptr(), nrm, nadd, out.data_ptr())
         self.ctx.synchronize()              # raises if a row was not a tree
         return out.cpu().numpy().astype(bool)
+
+    def link_loads(self, export, tree, layout, rows, dsts, weights=None, to_root=False,
+                   timing=False):
+        """Per-link loads of a demand routed over device tree rows (loads.hip,
+        sdnr_link_loads): numpy uint64 [E] in the CSR's edge order.
+
+        ``tree``: [k, V] int32 device tensor -- tree words of ``layout``
+        (PORT16 / SLOT) or int32 parents (INT32); pair i is routed in row
+        ``rows[i]`` to dense switch ``dsts[i]`` and weighs ``weights[i]``
+        (u64, None: 1).  ``to_root``: the rows are per-destination next-hop
+        rows (INT32) and ``dsts`` the pairs' source switches.  The pairs are
+        sorted by row here; only the E load words come back."""
+        self.load(export)
+        t = self._torch
+        E = int(export.csr.E)
+        rows = np.asarray(rows, np.int64)
+        nrows = int(tree.shape[0])
+        if rows.size == 0 or nrows == 0 or E == 0:
+            return np.zeros(E, np.uint64)
+        if rows.min() < 0 or rows.max() >= nrows:
+            raise ValueError("link_loads: a pair names a row outside the table")
+        order, off = _pairs_by_row(rows, nrows)
+        V = int(export.csr.V)
+        d = np.asarray(dsts, np.int64)[order]
+        d = np.where((d < 0) | (d >= V), -1, d).astype(np.int32)
+        tree = tree.contiguous()
+        d_off = t.from_numpy(off).to(self.dev)
+        d_dst = t.from_numpy(d).to(self.dev)
+        d_w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights, np.uint64)[order])
+            d_w = t.from_numpy(w.view(np.int64)).to(self.dev)
+        load = t.zeros(E, dtype=t.int64, device=self.dev)
+        lay = {PORT16: _native.TREE_PORT16, SLOT: _native.TREE_SLOT,
+               INT32: _native.TREE_INT32}[layout]
+        self._ready()
+        self.ctx.link_loads_device(tree.data_ptr(), lay, nrows, d_off.data_ptr(), d_dst.data_ptr(),
+                                   d_w.data_ptr() if d_w is not None else 0, load.data_ptr(),
+                                   to_root=to_root, timing=timing)
+        self.ctx.synchronize()              # raises if a row was not a tree
+        return load.cpu().numpy().view(np.uint64)
 
     def edge_ports(self, ends, ports):
         """Flood-port mask (sdnr_edge_ports, reference topology.py:150-155):

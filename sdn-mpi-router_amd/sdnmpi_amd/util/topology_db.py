@@ -26,7 +26,8 @@ first route query raises (``sdnmpi_amd._native.NativeUnavailable`` /
 
 import numpy as np
 
-from ..engine import RouteEngine, TableCache, _host, _take, shortest_paths_lex, tree_path
+from ..engine import (INT32, RouteEngine, TableCache, _gather, _host, _take, _torch, _u16,
+                      shortest_paths_lex, tree_path)
 from ..graph import TrackedDict, Versions, export_graph, update_export
 from ..incremental import edge_diff
 
@@ -35,10 +36,69 @@ try:   # the reference takes OFPP_LOCAL from Ryu's OpenFlow 1.0 module (:5)
 except Exception:   # noqa: BLE001 - Ryu is not a dependency of the engine
     OFPP_LOCAL = 0xfffe
 
-__all__ = ["TopologyDB", "OFPP_LOCAL", "sdn_mpi_mac"]
+__all__ = ["TopologyDB", "LinkLoads", "OFPP_LOCAL", "sdn_mpi_mac"]
 
 _INF = 0xFFFF
+_U64 = (1 << 64) - 1
 TABLE_SLICE_ENTRIES = 1 << 24     # table entries decoded per slice by route_tables()
+
+
+class LinkLoads(object):
+    """Predicted traffic per link (:meth:`TopologyDB.link_loads`).
+
+    One record per link of the switch graph, in the CSR's order (ascending
+    source dpid, then destination dpid), zeros included: ``src_dpid``,
+    ``dst_dpid``, ``port`` (``links[src][dst].src.port_no``) and ``load``
+    (uint64).  The last hops -- a route's entry on its destination switch,
+    out of the host's port or ``OFPP_LOCAL`` -- are ``host_dpid``,
+    ``host_port``, ``host_load``: the nonzero ones, ascending."""
+
+    def __init__(self, dpids, esrc, edst, port, load, hsw, hport, hload):
+        self._dpids = dpids
+        self._esrc, self._hsw = esrc, np.asarray(hsw, np.int64)
+        self.src_dpid = dpids[esrc]
+        self.dst_dpid = dpids[edst]
+        self.port = port
+        self.load = load
+        self.host_dpid = dpids[self._hsw]
+        self.host_port = np.asarray(hport, np.int64)
+        self.host_load = hload
+
+    def as_dict(self):
+        """{(dpid, out_port): load} of the nonzero entries, links and last
+        hops alike: the weighted count of the ``(dpid, out_port)`` tuples
+        ``find_route`` returns for the pairs."""
+        out = {}
+        nz = np.nonzero(self.load)[0]
+        for d, p, x in zip(self.src_dpid[nz].tolist(), self.port[nz].tolist(),
+                           self.load[nz].tolist()):
+            out[(d, p)] = (out.get((d, p), 0) + x) & _U64
+        for d, p, x in zip(self.host_dpid.tolist(), self.host_port.tolist(),
+                           self.host_load.tolist()):
+            out[(d, p)] = (out.get((d, p), 0) + x) & _U64
+        return out
+
+    def per_switch(self):
+        """(dpids, total): every switch of the graph (ascending dpid) and the
+        load leaving it, last hops included.  With unit weights and distinct
+        pairs ``total`` is the number of flow entries the router would
+        install on each switch."""
+        total = np.zeros(self._dpids.shape[0], np.uint64)
+        np.add.at(total, self._esrc, self.load)
+        np.add.at(total, self._hsw, self.host_load)
+        return self._dpids, total
+
+
+def _weights(weights, n):
+    """u64 weights of n pairs (None: ones); negative or oversized: ValueError."""
+    if weights is None:
+        return np.ones(n, np.uint64)
+    ws = [int(x) for x in weights]
+    if len(ws) != n:
+        raise ValueError("one weight per pair")
+    if any(x < 0 or x > _U64 for x in ws):
+        raise ValueError("weights are unsigned 64-bit integers")
+    return np.array(ws, np.uint64) if ws else np.zeros(0, np.uint64)
 
 
 class TopologyDB(object):
@@ -516,6 +576,147 @@ class TopologyDB(object):
         sr = np.asarray(src_r, np.int64)[pid] if pid.size else np.zeros(0, np.int64)
         dr = np.asarray(dst_r, np.int64)[pid] if pid.size else np.zeros(0, np.int64)
         return dpids, off, sr, dr, pt, last
+
+    # -- predicted link loads -------------------------------------------
+    def _switch_pair_loads(self, ex, sv, dv, w, route):
+        """(load uint64 [E], reach bool [n]) of switch pairs (dense ids sv ->
+        dv, weights w u64) routed the default way (per-source trees) or along
+        routes[0] of the shortest mode (per-destination next-hop rows): one
+        sdnr_link_loads call per budget-sized chunk of table rows."""
+        if route not in ("default", "shortest"):
+            raise ValueError("route must be 'default' or 'shortest'")
+        E, V = int(ex.csr.E), int(ex.csr.V)
+        load = np.zeros(E, np.uint64)
+        reach = np.zeros(sv.shape[0], bool)
+        if sv.size == 0:
+            return load, reach
+        c = self._cache
+        short = route == "shortest"
+        store = c.sp if short else c.dfs
+        key, other = (dv, sv) if short else (sv, dv)       # table row / vertex inside it
+        want = sorted(set(key.tolist()))
+        batch = self._host_vertices(ex) if self._batch else ()
+        step = max(1, store.cap() - 1) if store.row_bytes else len(want)
+        if short:      # the next-hop rows are widened to int32: bounded temporaries
+            step = min(step, max(1, TABLE_SLICE_ENTRIES // max(1, V)))
+        for c0 in range(0, len(want), step):      # a budget's worth of rows at a time
+            chunk = want[c0:c0 + step]
+            get = c.sp_rows if short else c.dfs_rows
+            tabs = get(self.engine, chunk, batch if c0 == 0 else ())
+            mine = np.nonzero(np.isin(key, np.asarray(chunk, np.int64)))[0]
+            slots = np.asarray([store.row[v] for v in key[mine].tolist()], np.int64)
+            # hops / distance planes hold -1 (u16 0xFFFF as int16) where unreached
+            reach[mine] = _gather(tabs[0] if short else tabs[-1], slots, other[mine]) != -1
+            if short:
+                urows, inv = np.unique(slots, return_inverse=True)
+                nh = _take(tabs[1], urows)
+                nh = _u16(nh) if V <= 0xFFFF else nh
+                nh = nh.astype(np.int32) if isinstance(nh, np.ndarray) else \
+                    nh.to(dtype=_torch().int32)
+                load += self.engine.link_loads(ex, nh, INT32, inv, other[mine], w[mine],
+                                               to_root=True)
+            else:
+                load += self.engine.link_loads(ex, tabs[0], c.layout, slots, other[mine],
+                                               w[mine])
+        return load, reach
+
+    def _link_loads_result(self, ex, load, hkey, hload):
+        """LinkLoads of CSR-ordered link loads plus last hops ``hkey`` ([k, 2]
+        int64 rows (dense switch, port), unique) with loads ``hload``."""
+        csr = ex.csr
+        rp = np.asarray(csr.row_ptr, np.int64)
+        esrc = np.repeat(np.arange(csr.V, dtype=np.int64), np.diff(rp))
+        dp = np.asarray(csr.dpids)
+        nz = np.nonzero(hload)[0]
+        hkey, hload = hkey[nz], hload[nz]
+        return LinkLoads(dp, esrc, np.asarray(csr.col, np.int64), np.asarray(csr.port, np.int64),
+                         load, hkey[:, 0], hkey[:, 1], hload)
+
+    def link_loads(self, pairs, weights=None, route="default"):
+        """How much traffic crosses each link when every (src_mac, dst_mac)
+        pair of ``pairs`` sends ``weights[i]`` (non-negative ints, e.g. bytes;
+        None: 1 each) along the controller's route -- the per-port traffic
+        ``sdnmpi/monitor.py`` would log for the flows ``Router.
+        _add_flows_for_path`` installs (reference ``router.py:83-104``) -- as a
+        :class:`LinkLoads`.
+
+        Defining property: ``link_loads(pairs, w).as_dict()`` equals the sum
+        over i of ``w[i]`` on every ``(dpid, out_port)`` entry of
+        ``find_route(*pairs[i])``; with ``route="shortest"`` the entries are
+        those of ``find_route(*pairs[i], multiple=True)[0]``.  Unknown hosts
+        and unreachable pairs contribute nothing (``find_route`` returns
+        ``[]``); repeated pairs add.  No flow entry is built: the MAC pairs
+        are summed to switch pairs, the GPU turns each table row's demand
+        into subtree sums (loads.hip), and the last hops -- (destination
+        switch, host port or OFPP_LOCAL) -- are added here.  Sums are
+        unsigned 64-bit and wrap."""
+        pairs = list(pairs)
+        n = len(pairs)
+        w = _weights(weights, n)
+        ex = self.graph()
+        V = int(ex.csr.V)
+        sv = np.full(n, -1, np.int64)
+        dv = np.full(n, -1, np.int64)
+        last = np.zeros(n, np.int64)
+        for i, (a, b) in enumerate(pairs):
+            ea, eb = self._endpoint(a), self._endpoint(b)
+            if ea is None or eb is None:
+                continue
+            sv[i] = ex.index[ea[0]]
+            dv[i] = ex.index[eb[0]]
+            last[i] = self._last_hop(eb[0], eb[1], b)[1]
+        ok = np.nonzero(sv >= 0)[0]
+        # MAC pairs -> switch pairs, weights summed
+        skey, inv = np.unique(sv[ok] * max(1, V) + dv[ok], return_inverse=True)
+        sw = np.zeros(skey.shape[0], np.uint64)
+        np.add.at(sw, inv, w[ok])
+        load, reach = self._switch_pair_loads(ex, skey // max(1, V), skey % max(1, V), sw, route)
+        got = ok[reach[inv]] if ok.size else ok              # pairs whose route exists
+        hkey, hinv = np.unique(np.stack([dv[got], last[got]], 1), axis=0, return_inverse=True)
+        hload = np.zeros(hkey.shape[0], np.uint64)
+        np.add.at(hload, hinv.reshape(-1), w[got])
+        return self._link_loads_result(ex, load, hkey.reshape(-1, 2), hload)
+
+    def all_pairs_link_loads(self, route="default"):
+        """:meth:`link_loads` over every ordered pair of distinct hosts with
+        weight 1 (all-to-all traffic), from the per-switch host counts: the
+        demand of switch pair (s, d) is hosts(s) * hosts(d), never expanded
+        to MAC pairs (764 M host pairs on the k=48 fat-tree are 1,152^2
+        switch demands)."""
+        if any(self._mac_to_int(m) in self.switches for m in self.hosts):
+            # a host MAC that names a switch resolves to its local port
+            macs = list(self.hosts)
+            return self.link_loads([(a, b) for a in macs for b in macs if a != b], None, route)
+        ex = self.graph()
+        hv = np.asarray(self._host_vertices(ex), np.int64)
+        hc = np.asarray(ex.host_count, np.int64)
+        n = hv.shape[0]
+        sv, dv = np.repeat(hv, n), np.tile(hv, n)
+        w = (hc[sv] * (hc[dv] - (sv == dv))).astype(np.uint64)
+        load, reach = self._switch_pair_loads(ex, sv, dv, w, route)
+        # hosts that reach switch d: every host on d gets that many flows, less itself
+        cnt = (reach.reshape(n, n) * hc[hv][:, None]).sum(0)
+        into = np.zeros(int(ex.csr.V), np.int64)
+        into[hv] = cnt - 1
+        hd = np.asarray([ex.index[h.port.dpid] for h in self.hosts.values()], np.int64)
+        hp = np.asarray([int(h.port.port_no) for h in self.hosts.values()], np.int64)
+        hkey, hinv = np.unique(np.stack([hd, hp], 1).reshape(-1, 2), axis=0, return_inverse=True)
+        hload = np.zeros(hkey.shape[0], np.uint64)
+        np.add.at(hload, hinv.reshape(-1), into[hd].astype(np.uint64))
+        return self._link_loads_result(ex, load, hkey.reshape(-1, 2), hload)
+
+    def mpi_link_loads(self, rank_to_mac, traffic=None, route="default"):
+        """:meth:`link_loads` of an MPI job: ``traffic`` = {(src_rank,
+        dst_rank): weight} between the ranks of ``rank_to_mac`` (a rank the
+        map lacks is an unknown host); None: every ordered rank pair i != j
+        with weight 1 -- the pairs of :meth:`mpi_flow_entries`."""
+        if traffic is None:
+            ranks = sorted(rank_to_mac)
+            pairs = [(rank_to_mac[a], rank_to_mac[b]) for a in ranks for b in ranks if a != b]
+            return self.link_loads(pairs, None, route)
+        items = [(k, x) for k, x in traffic.items() if k[0] in rank_to_mac and k[1] in rank_to_mac]
+        pairs = [(rank_to_mac[a], rank_to_mac[b]) for (a, b), _ in items]
+        return self.link_loads(pairs, [x for _, x in items], route)
 
     def find_routes(self, pairs, multiple=False):
         """find_route over many (src_mac, dst_mac) pairs; tables are computed
