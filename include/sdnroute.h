@@ -49,6 +49,9 @@ extern "C" {
                                  derived walk tables are reused */
 #define SDNR_LOADS_TO_ROOT 0x8u /* sdnr_link_loads: rows are per-destination
                                  next-hop rows (edges point toward the root) */
+#define SDNR_LOADS_SPLIT_HOP 0x10u /* sdnr_ecmp_link_loads: every switch splits
+                                 evenly over its next hops (default: evenly
+                                 over the pair's shortest routes) */
 
 #define SDNR_UNREACHED (-1)
 #define SDNR_DIST_INF  0xFFFFu
@@ -314,6 +317,43 @@ int sdnr_route_expand_packed(sdnr_ctx *ctx, const int32_t *parent, const int32_t
 int sdnr_link_loads(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nrows,
                     const int64_t *pair_off, const int32_t *dsts, const uint64_t *weight,
                     uint64_t *load, uint32_t flags);
+
+/* Per-link loads of a traffic matrix under ECMP: every pair's traffic is split
+ * over ALL its shortest routes -- the set find_route(multiple=True) returns
+ * (reference _find_routes_bfs, sdnmpi/util/topology_db.py:86-122) -- where
+ * sdnr_link_loads puts it on one.  No route is enumerated and no count
+ * saturates: per destination row the shortest-route counts sigma[] are a level
+ * DP in double, and the demand is pushed down the shortest-path DAG level by
+ * level, O(E) per row whatever the number of pairs or routes.
+ *   dist      [nrows][V] u16 distance rows of sdnr_shortest_tables, row r = the
+ *             hop counts toward one destination (SDNR_DIST_INF: unreached);
+ *   pair_off  [nrows + 1] int64: the pairs of row r are srcs[pair_off[r] ..
+ *             pair_off[r+1]) (source switches, dense ids) with weight[] (u64,
+ *             e.g. bytes) at the same indices; weight NULL: all 1.  Weights
+ *             are converted to double: values >= 2^53 round to nearest;
+ *   load      [E] double in the uploaded CSR's edge order.  The call ADDS into
+ *             load (the caller zeroes it; row chunks of one batch sum up).
+ * A vertex x of level L = dist[x] > 0 has as next hops its out-neighbours of
+ * level L - 1.  Default (route split): each of the pair's sigma[s] shortest
+ * routes carries w / sigma[s], i.e. x sends the share sigma[n] / sigma[x] of
+ * the flow through it over link x -> n.  SDNR_LOADS_SPLIT_HOP: x sends 1 /
+ * (number of its next hops) over each (an OpenFlow select group per switch).
+ * load[e(x -> n)] receives what is sent over it.  Unreachable sources, sources
+ * outside [0, V), the pair s == d and zero weights contribute nothing;
+ * repeated pairs add.  Sums are f64 atomics: every term is non-negative (the
+ * relative error is a few ulp per level), but the last bits depend on the
+ * order of arrival and may differ between runs unless every partial sum is
+ * exact (power-of-two shares, integer weights).  No NaN or Inf reaches load.
+ * Device pointers only (flags must hold SDNR_DEVICE_PTRS); asynchronous on
+ * the context stream (pair_off[0] and pair_off[nrows] are read back first:
+ * not monotone is SDNR_ERR_INVAL); on a multi-device context it runs on the
+ * primary device.  nrows == 0 or no pairs: SDNR_OK, nothing touched.  A row
+ * that is not a BFS labelling of the graph (a vertex of level > 0 without a
+ * next hop, a level >= V, a route count above the double range) is reported
+ * by sdnr_synchronize as SDNR_ERR_INVAL; that vertex's flow is dropped. */
+int sdnr_ecmp_link_loads(sdnr_ctx *ctx, const uint16_t *dist, int32_t nrows,
+                         const int64_t *pair_off, const int32_t *srcs, const uint64_t *weight,
+                         double *load, uint32_t flags);
 
 /* Flood ports (TopologyManager._is_edge_port / _do_broadcast, reference
  * sdnmpi/topology.py:150-177): is_edge[i] = 1 iff ports[i] is neither end of

@@ -56,6 +56,11 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "uploaded graph (an ancestor chain longer than V, a parent that is "
                              "no vertex, a tree link the graph lacks) or pair_off is not "
                              "monotone: loads invalid");
+        if (h & kErrEcmpLoads)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_link_loads: a distance row is not a BFS "
+                             "labelling of the uploaded graph (a vertex without a next hop, a "
+                             "level >= V, a route count above the double range) or pair_off is "
+                             "not monotone: loads invalid");
         if (h & kErrLastPort)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_route_expand_packed: a last port outside "
                              "[0, 0xFFFF] (u32 entries hold 16-bit ports): entries invalid");
@@ -1138,6 +1143,37 @@ int sdnr_link_loads(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nro
     ctx->timed = (flags & SDNR_TIMING) != 0;
     return sdnr_launch_link_loads(ctx, tree, layout, to_root, nrows, pair_off, lo, hi, dsts,
                                   weight, load);
+}
+
+int sdnr_ecmp_link_loads(sdnr_ctx *ctx, const uint16_t *dist, int32_t nrows,
+                         const int64_t *pair_off, const int32_t *srcs, const uint64_t *weight,
+                         double *load, uint32_t flags)
+{
+    CHECK_CTX(ctx);
+    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_ecmp_link_loads: no graph uploaded");
+    if (!(flags & SDNR_DEVICE_PTRS))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_link_loads: device pointers only");
+    if (nrows < 0) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_link_loads: negative count");
+    if (nrows == 0) return SDNR_OK;
+    if (!dist || !pair_off || !load)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_link_loads: null pointer");
+    SDNR_HIP(hipSetDevice(ctx->device));
+    // the bounds of the pair list: pair_off[0], pair_off[nrows] (two int64)
+    int w[4];
+    int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off), 2, w);
+    if (!rc) rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off + nrows), 2, w + 2);
+    if (rc) return rc;
+    const int64_t lo = (int64_t)(((uint64_t)(uint32_t)w[1] << 32) | (uint32_t)w[0]);
+    const int64_t hi = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
+    if (lo < 0 || hi < lo)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_link_loads: pair_off not monotone "
+                         "(pair_off[0]=%lld, pair_off[%d]=%lld)", (long long)lo, nrows,
+                         (long long)hi);
+    if (hi == lo || ctx->V == 0) return SDNR_OK;
+    if (!srcs) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_link_loads: null pointer");
+    ctx->timed = (flags & SDNR_TIMING) != 0;
+    return sdnr_launch_ecmp_link_loads(ctx, dist, nrows, pair_off, lo, hi, srcs, weight, load,
+                                       (flags & SDNR_LOADS_SPLIT_HOP) != 0);
 }
 
 int sdnr_shortest_tables(sdnr_ctx *ctx, const int32_t *dst, int32_t ndst, uint16_t *dist,

@@ -171,6 +171,13 @@ constexpr int kErrLoadsTree = 4096; // sdnr_link_loads: a row is not a tree of t
 // (24 bytes per vertex and workgroup, at most kLoadsScratchBytes in all)
 constexpr int kLoadsLdsMaxV = 8000;
 constexpr size_t kLoadsScratchBytes = (size_t)1 << 30;
+constexpr int kErrEcmpLoads = 8192; // sdnr_ecmp_link_loads: a dist row is no BFS labelling / bad offsets
+
+// sdnr_ecmp_link_loads keeps a row's levels, route counts and flows in LDS
+// (16 control bytes + 18 per vertex: 162,016 of the CU's 163,840) up to this V,
+// else the counts and flows in global scratch (16 bytes per vertex and
+// workgroup, at most kLoadsScratchBytes in all)
+constexpr int kEcmpLoadsLdsMaxV = 9000;
 
 // error plumbing (capi.hip)
 int sdnr_fail(int code, const char *fmt, ...);
@@ -239,5 +246,10 @@ int sdnr_launch_link_loads(sdnr_ctx *ctx, const void *d_tree, int32_t layout, bo
                            int32_t nrows, const int64_t *d_pair_off, int64_t pair_lo,
                            int64_t pair_hi, const int32_t *d_dsts, const uint64_t *d_weight,
                            uint64_t *d_load);
+// per-link loads of a demand split over every shortest route (ecmp_loads.hip)
+int sdnr_launch_ecmp_link_loads(sdnr_ctx *ctx, const uint16_t *d_dist, int32_t nrows,
+                                const int64_t *d_pair_off, int64_t pair_lo, int64_t pair_hi,
+                                const int32_t *d_srcs, const uint64_t *d_weight, double *d_load,
+                                bool hop);
 int sdnr_launch_edge_ports(sdnr_ctx *ctx, const uint64_t *d_ends, int32_t nends,
                            const uint64_t *d_ports, int32_t nports, uint8_t *d_is_edge);

@@ -26,6 +26,7 @@ DEVICE_PTRS = 0x1
 TIMING = 0x2
 SAME_TABLES = 0x4        # route expansion: the previous call's parent / port tables
 LOADS_TO_ROOT = 0x8      # sdnr_link_loads: per-destination next-hop rows
+LOADS_SPLIT_HOP = 0x10   # sdnr_ecmp_link_loads: even split over a switch's next hops
 UNREACHED = -1
 DIST_INF = 0xFFFF
 TREE_NONE = 0xFFFFFFFF
@@ -44,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_ecmp_routes",
     "sdnr_last_kernel_ms", "sdnr_last_kernel", "sdnr_last_launches", "sdnr_last_sweeps",
     "sdnr_edge_ports", "sdnr_dfs_rows_affected", "sdnr_link_loads",
+    "sdnr_ecmp_link_loads",
 )
 
 
@@ -100,6 +102,7 @@ def _bind(L):
         "sdnr_edge_ports": ([vp, vp, i32, vp, i32, vp, u32], c_int),
         "sdnr_dfs_rows_affected": ([vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, u32], c_int),
         "sdnr_link_loads": ([vp, vp, i32, i32, vp, vp, vp, vp, u32], c_int),
+        "sdnr_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, vp, u32], c_int),
     }
     # an A/B build named by SDNROUTE_LIB may predate some entry points: those
     # stay unbound (calling one raises AttributeError); the in-tree library
@@ -429,6 +432,21 @@ class Context(object):
             self._h, ctypes.c_void_p(tree_ptr) if tree_ptr else None, int(layout), int(nrows),
             ctypes.c_void_p(pair_off_ptr) if pair_off_ptr else None,
             ctypes.c_void_p(dsts_ptr) if dsts_ptr else None,
+            ctypes.c_void_p(weight_ptr) if weight_ptr else None,
+            ctypes.c_void_p(load_ptr) if load_ptr else None, flags))
+
+    def ecmp_link_loads_device(self, dist_ptr, nrows, pair_off_ptr, srcs_ptr, weight_ptr,
+                               load_ptr, hop=False, timing=False):
+        """Add the per-link loads of a demand split over every shortest route
+        of [nrows][V] u16 distance rows into ``load`` (f64 [E], CSR edge
+        order; the caller zeroes it): sdnr_ecmp_link_loads, device pointers,
+        asynchronous.  ``weight_ptr`` 0: every pair weighs 1; ``hop``: split
+        evenly per switch (SDNR_LOADS_SPLIT_HOP) instead of per route."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_SPLIT_HOP if hop else 0)
+        _check(self._lib.sdnr_ecmp_link_loads(
+            self._h, ctypes.c_void_p(dist_ptr) if dist_ptr else None, int(nrows),
+            ctypes.c_void_p(pair_off_ptr) if pair_off_ptr else None,
+            ctypes.c_void_p(srcs_ptr) if srcs_ptr else None,
             ctypes.c_void_p(weight_ptr) if weight_ptr else None,
             ctypes.c_void_p(load_ptr) if load_ptr else None, flags))
 

@@ -41,7 +41,7 @@ from .graph import empty_csr
 
 __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "shortest_paths_lex", "count_shortest_paths", "ECMP_LIMIT", "DEFAULT_TABLE_BUDGET", "tree_layout", "dfs_row_bytes",
-           "sp_row_bytes", "link_loads_host"]
+           "sp_row_bytes", "link_loads_host", "ecmp_link_loads_host"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -327,6 +327,73 @@ def link_loads_host(csr, tree, layout, rows, dsts, weights=None, to_root=False):
     if not np.array_equal(keys[e], k):
         raise ValueError("link_loads_host: a tree link the graph does not have")
     np.add.at(load, e, acc[r, v])
+    return load
+
+
+SPLITS = ("route", "hop")
+
+
+def ecmp_link_loads_host(csr, dist, rows, srcs, weights=None, split="route"):
+    """numpy float64 restatement of sdnr_ecmp_link_loads (the CPU tests' engine
+    double and an independent check of ecmp_loads.hip): float64 [E] loads of
+    pairs (distance row ``rows[i]`` of ``dist``, source switch ``srcs[i]``,
+    weight ``weights[i]`` or 1) split over every shortest route.
+
+    ``dist``: [k, V] hop counts toward each row's destination, uint16 or the
+    cache's int16-holding-u16 plane (0xFFFF / -1: unreached).  Per used row
+    the links of the shortest-path DAG (level L -> L - 1) are sorted by level
+    once; sigma (shortest-route counts; ``split="hop"``: next-hop counts) is
+    summed per level ascending with ``np.bincount``, then the flow is pushed
+    top level first, a whole level's links at a time.  A row that is not a
+    BFS labelling of the graph (a reached vertex of level > 0 without a next
+    hop, a route count beyond the double range) raises ValueError."""
+    if split not in SPLITS:
+        raise ValueError("split must be 'route' or 'hop'")
+    V, E = int(csr.V), int(csr.E)
+    load = np.zeros(E, np.float64)
+    rows = np.asarray(rows, np.int64)
+    srcs = np.asarray(srcs, np.int64)
+    if rows.size == 0 or E == 0:
+        return load
+    w = np.ones(rows.shape[0], np.float64) if weights is None else \
+        np.asarray(weights, np.uint64).astype(np.float64)
+    dist = np.asarray(dist)
+    if dist.dtype == np.int16:
+        dist = dist.view(np.uint16)
+    rp = np.asarray(csr.row_ptr, np.int64)
+    esrc = np.repeat(np.arange(V, dtype=np.int64), np.diff(rp))
+    edst = np.asarray(csr.col, np.int64)
+    ok = np.nonzero((srcs >= 0) & (srcs < V) & (w > 0))[0]
+    ok = ok[np.argsort(rows[ok], kind="stable")]           # the pairs grouped by row
+    used, first = np.unique(rows[ok], return_index=True)
+    bounds = np.append(first, ok.shape[0])
+    for k, r in enumerate(used.tolist()):
+        lv = dist[r].astype(np.int64)
+        lv[lv == 0xFFFF] = -1
+        mine = ok[bounds[k]:bounds[k + 1]]
+        s = srcs[mine]
+        keep = lv[s] > 0                                   # not unreached, not s == d
+        flow = np.bincount(s[keep], w[mine][keep], minlength=V).astype(np.float64)
+        top = int(lv.max())
+        dag = np.nonzero((lv[esrc] > 0) & (lv[edst] == lv[esrc] - 1))[0]
+        dag = dag[np.argsort(lv[esrc[dag]], kind="stable")]
+        ends = np.searchsorted(lv[esrc[dag]], np.arange(top + 2))   # level L: ends[L]:ends[L+1]
+        sigma = np.zeros(V, np.float64)
+        if split == "hop":
+            sigma += np.bincount(esrc[dag], minlength=V)
+        else:
+            sigma[lv == 0] = 1.0
+            for L in range(1, top + 1):
+                e = dag[ends[L]:ends[L + 1]]
+                sigma += np.bincount(esrc[e], sigma[edst[e]], minlength=V)
+        if ((lv > 0) & ~(sigma > 0)).any() or not np.isfinite(sigma).all():
+            raise ValueError("ecmp_link_loads_host: a row is not a BFS labelling of the graph")
+        for L in range(top, 0, -1):
+            e = dag[ends[L]:ends[L + 1]]
+            x, n = esrc[e], edst[e]
+            g = flow[x] / sigma[x] if split == "hop" else flow[x] * (sigma[n] / sigma[x])
+            load[e] += g                                   # (a link appears once per level)
+            flow += np.bincount(n, g, minlength=V)
     return load
 
 
@@ -617,6 +684,53 @@ class RouteEngine(object):
                                    to_root=to_root, timing=timing)
         self.ctx.synchronize()              # raises if a row was not a tree
         return load.cpu().numpy().view(np.uint64)
+
+    def ecmp_link_loads(self, export, dist, rows, srcs, weights=None, split="route",
+                        timing=False):
+        """Per-link loads of a demand split over every shortest route
+        (ecmp_loads.hip, sdnr_ecmp_link_loads): numpy float64 [E] in the CSR's
+        edge order.
+
+        ``dist``: [k, V] device tensor of distance rows (int16 holding u16, as
+        ``shortest_tables`` and the table cache keep them; rows without pairs
+        are skipped); pair i enters at dense switch ``srcs[i]`` of row
+        ``rows[i]`` and weighs ``weights[i]`` (u64, None: 1).  ``split``:
+        "route" (even over the pair's shortest routes) or "hop" (even over
+        each switch's next hops).  The pairs are sorted by row here; only the
+        E load words come back.  Sums are f64 atomics: equal to the host
+        restatement within rounding, not bit-reproducible."""
+        if split not in SPLITS:
+            raise ValueError("split must be 'route' or 'hop'")
+        self.load(export)
+        t = self._torch
+        E = int(export.csr.E)
+        rows = np.asarray(rows, np.int64)
+        nrows = int(dist.shape[0])
+        if rows.size == 0 or nrows == 0 or E == 0:
+            return np.zeros(E, np.float64)
+        if rows.min() < 0 or rows.max() >= nrows:
+            raise ValueError("ecmp_link_loads: a pair names a row outside the table")
+        if dist.element_size() != 2:
+            raise ValueError("ecmp_link_loads: distance rows are 16-bit")
+        order, off = _pairs_by_row(rows, nrows)
+        V = int(export.csr.V)
+        s = np.asarray(srcs, np.int64)[order]
+        s = np.where((s < 0) | (s >= V), -1, s).astype(np.int32)
+        dist = dist.contiguous()
+        d_off = t.from_numpy(off).to(self.dev)
+        d_src = t.from_numpy(s).to(self.dev)
+        d_w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights, np.uint64)[order])
+            d_w = t.from_numpy(w.view(np.int64)).to(self.dev)
+        load = t.zeros(E, dtype=t.float64, device=self.dev)
+        self._ready()
+        self.ctx.ecmp_link_loads_device(dist.data_ptr(), nrows, d_off.data_ptr(),
+                                        d_src.data_ptr(),
+                                        d_w.data_ptr() if d_w is not None else 0,
+                                        load.data_ptr(), hop=split == "hop", timing=timing)
+        self.ctx.synchronize()              # raises if a row was no BFS labelling
+        return load.cpu().numpy()
 
     def edge_ports(self, ends, ports):
         """Flood-port mask (sdnr_edge_ports, reference topology.py:150-155):

@@ -36,7 +36,7 @@ try:   # the reference takes OFPP_LOCAL from Ryu's OpenFlow 1.0 module (:5)
 except Exception:   # noqa: BLE001 - Ryu is not a dependency of the engine
     OFPP_LOCAL = 0xfffe
 
-__all__ = ["TopologyDB", "LinkLoads", "OFPP_LOCAL", "sdn_mpi_mac"]
+__all__ = ["TopologyDB", "LinkLoads", "SplitLinkLoads", "OFPP_LOCAL", "sdn_mpi_mac"]
 
 _INF = 0xFFFF
 _U64 = (1 << 64) - 1
@@ -86,6 +86,35 @@ class LinkLoads(object):
         total = np.zeros(self._dpids.shape[0], np.uint64)
         np.add.at(total, self._esrc, self.load)
         np.add.at(total, self._hsw, self.host_load)
+        return self._dpids, total
+
+
+class SplitLinkLoads(LinkLoads):
+    """Predicted traffic per link under ECMP (:meth:`TopologyDB.
+    ecmp_link_loads`): the records of :class:`LinkLoads` with a float64
+    ``load`` -- a pair's traffic is split over its shortest routes, so a link
+    carries fractions of weights.  ``host_load`` stays exact uint64: every
+    route of a pair ends on the same last hop."""
+
+    def as_dict(self):
+        """{(dpid, out_port): float load} of the nonzero entries, links and
+        last hops alike."""
+        out = {}
+        nz = np.nonzero(self.load)[0]
+        for d, p, x in zip(self.src_dpid[nz].tolist(), self.port[nz].tolist(),
+                           self.load[nz].tolist()):
+            out[(d, p)] = out.get((d, p), 0.0) + x
+        for d, p, x in zip(self.host_dpid.tolist(), self.host_port.tolist(),
+                           self.host_load.tolist()):
+            out[(d, p)] = out.get((d, p), 0.0) + float(x)
+        return out
+
+    def per_switch(self):
+        """(dpids, total float64): every switch of the graph (ascending dpid)
+        and the load leaving it, last hops included."""
+        total = np.zeros(self._dpids.shape[0], np.float64)
+        np.add.at(total, self._esrc, self.load)
+        np.add.at(total, self._hsw, self.host_load.astype(np.float64))
         return self._dpids, total
 
 
@@ -620,7 +649,7 @@ class TopologyDB(object):
                                                w[mine])
         return load, reach
 
-    def _link_loads_result(self, ex, load, hkey, hload):
+    def _link_loads_result(self, ex, load, hkey, hload, cls=LinkLoads):
         """LinkLoads of CSR-ordered link loads plus last hops ``hkey`` ([k, 2]
         int64 rows (dense switch, port), unique) with loads ``hload``."""
         csr = ex.csr
@@ -629,27 +658,16 @@ class TopologyDB(object):
         dp = np.asarray(csr.dpids)
         nz = np.nonzero(hload)[0]
         hkey, hload = hkey[nz], hload[nz]
-        return LinkLoads(dp, esrc, np.asarray(csr.col, np.int64), np.asarray(csr.port, np.int64),
-                         load, hkey[:, 0], hkey[:, 1], hload)
+        return cls(dp, esrc, np.asarray(csr.col, np.int64), np.asarray(csr.port, np.int64),
+                   load, hkey[:, 0], hkey[:, 1], hload)
 
-    def link_loads(self, pairs, weights=None, route="default"):
-        """How much traffic crosses each link when every (src_mac, dst_mac)
-        pair of ``pairs`` sends ``weights[i]`` (non-negative ints, e.g. bytes;
-        None: 1 each) along the controller's route -- the per-port traffic
-        ``sdnmpi/monitor.py`` would log for the flows ``Router.
-        _add_flows_for_path`` installs (reference ``router.py:83-104``) -- as a
-        :class:`LinkLoads`.
-
-        Defining property: ``link_loads(pairs, w).as_dict()`` equals the sum
-        over i of ``w[i]`` on every ``(dpid, out_port)`` entry of
-        ``find_route(*pairs[i])``; with ``route="shortest"`` the entries are
-        those of ``find_route(*pairs[i], multiple=True)[0]``.  Unknown hosts
-        and unreachable pairs contribute nothing (``find_route`` returns
-        ``[]``); repeated pairs add.  No flow entry is built: the MAC pairs
-        are summed to switch pairs, the GPU turns each table row's demand
-        into subtree sums (loads.hip), and the last hops -- (destination
-        switch, host port or OFPP_LOCAL) -- are added here.  Sums are
-        unsigned 64-bit and wrap."""
+    def _pair_loads(self, pairs, weights, switch_loads, cls):
+        """The MAC-pair form shared by :meth:`link_loads` and
+        :meth:`ecmp_link_loads`: the pairs are resolved to switches, summed to
+        switch pairs, handed to ``switch_loads(ex, sv, dv, w)`` -> (load [E],
+        reach bool per switch pair), and the last hops -- (destination
+        switch, host port or OFPP_LOCAL) of the pairs whose route exists --
+        are added."""
         pairs = list(pairs)
         n = len(pairs)
         w = _weights(weights, n)
@@ -670,30 +688,29 @@ class TopologyDB(object):
         skey, inv = np.unique(sv[ok] * max(1, V) + dv[ok], return_inverse=True)
         sw = np.zeros(skey.shape[0], np.uint64)
         np.add.at(sw, inv, w[ok])
-        load, reach = self._switch_pair_loads(ex, skey // max(1, V), skey % max(1, V), sw, route)
+        load, reach = switch_loads(ex, skey // max(1, V), skey % max(1, V), sw)
         got = ok[reach[inv]] if ok.size else ok              # pairs whose route exists
         hkey, hinv = np.unique(np.stack([dv[got], last[got]], 1), axis=0, return_inverse=True)
         hload = np.zeros(hkey.shape[0], np.uint64)
         np.add.at(hload, hinv.reshape(-1), w[got])
-        return self._link_loads_result(ex, load, hkey.reshape(-1, 2), hload)
+        return self._link_loads_result(ex, load, hkey.reshape(-1, 2), hload, cls)
 
-    def all_pairs_link_loads(self, route="default"):
-        """:meth:`link_loads` over every ordered pair of distinct hosts with
-        weight 1 (all-to-all traffic), from the per-switch host counts: the
-        demand of switch pair (s, d) is hosts(s) * hosts(d), never expanded
-        to MAC pairs (764 M host pairs on the k=48 fat-tree are 1,152^2
-        switch demands)."""
+    def _all_pairs_loads(self, switch_loads, cls):
+        """The all-host-pairs form shared by :meth:`all_pairs_link_loads` and
+        :meth:`all_pairs_ecmp_link_loads`, from the per-switch host counts:
+        the demand of switch pair (s, d) is hosts(s) * hosts(d), never
+        expanded to MAC pairs.  None when a host MAC names a switch (it
+        resolves to the switch's local port: the caller takes the MAC-pair
+        form)."""
         if any(self._mac_to_int(m) in self.switches for m in self.hosts):
-            # a host MAC that names a switch resolves to its local port
-            macs = list(self.hosts)
-            return self.link_loads([(a, b) for a in macs for b in macs if a != b], None, route)
+            return None
         ex = self.graph()
         hv = np.asarray(self._host_vertices(ex), np.int64)
         hc = np.asarray(ex.host_count, np.int64)
         n = hv.shape[0]
         sv, dv = np.repeat(hv, n), np.tile(hv, n)
         w = (hc[sv] * (hc[dv] - (sv == dv))).astype(np.uint64)
-        load, reach = self._switch_pair_loads(ex, sv, dv, w, route)
+        load, reach = switch_loads(ex, sv, dv, w)
         # hosts that reach switch d: every host on d gets that many flows, less itself
         cnt = (reach.reshape(n, n) * hc[hv][:, None]).sum(0)
         into = np.zeros(int(ex.csr.V), np.int64)
@@ -703,20 +720,134 @@ class TopologyDB(object):
         hkey, hinv = np.unique(np.stack([hd, hp], 1).reshape(-1, 2), axis=0, return_inverse=True)
         hload = np.zeros(hkey.shape[0], np.uint64)
         np.add.at(hload, hinv.reshape(-1), into[hd].astype(np.uint64))
-        return self._link_loads_result(ex, load, hkey.reshape(-1, 2), hload)
+        return self._link_loads_result(ex, load, hkey.reshape(-1, 2), hload, cls)
+
+    @staticmethod
+    def _rank_pairs(rank_to_mac, traffic):
+        """(pairs, weights) of an MPI job's traffic: {(src_rank, dst_rank):
+        weight} between known ranks; None: every ordered rank pair, weight 1."""
+        if traffic is None:
+            ranks = sorted(rank_to_mac)
+            return [(rank_to_mac[a], rank_to_mac[b]) for a in ranks for b in ranks if a != b], None
+        items = [(k, x) for k, x in traffic.items() if k[0] in rank_to_mac and k[1] in rank_to_mac]
+        return [(rank_to_mac[a], rank_to_mac[b]) for (a, b), _ in items], [x for _, x in items]
+
+    def link_loads(self, pairs, weights=None, route="default"):
+        """How much traffic crosses each link when every (src_mac, dst_mac)
+        pair of ``pairs`` sends ``weights[i]`` (non-negative ints, e.g. bytes;
+        None: 1 each) along the controller's route -- the per-port traffic
+        ``sdnmpi/monitor.py`` would log for the flows ``Router.
+        _add_flows_for_path`` installs (reference ``router.py:83-104``) -- as a
+        :class:`LinkLoads`.
+
+        Defining property: ``link_loads(pairs, w).as_dict()`` equals the sum
+        over i of ``w[i]`` on every ``(dpid, out_port)`` entry of
+        ``find_route(*pairs[i])``; with ``route="shortest"`` the entries are
+        those of ``find_route(*pairs[i], multiple=True)[0]``.  Unknown hosts
+        and unreachable pairs contribute nothing (``find_route`` returns
+        ``[]``); repeated pairs add.  No flow entry is built: the MAC pairs
+        are summed to switch pairs, the GPU turns each table row's demand
+        into subtree sums (loads.hip), and the last hops -- (destination
+        switch, host port or OFPP_LOCAL) -- are added here.  Sums are
+        unsigned 64-bit and wrap."""
+        return self._pair_loads(
+            pairs, weights, lambda ex, sv, dv, w: self._switch_pair_loads(ex, sv, dv, w, route),
+            LinkLoads)
+
+    def all_pairs_link_loads(self, route="default"):
+        """:meth:`link_loads` over every ordered pair of distinct hosts with
+        weight 1 (all-to-all traffic), from the per-switch host counts: the
+        demand of switch pair (s, d) is hosts(s) * hosts(d), never expanded
+        to MAC pairs (764 M host pairs on the k=48 fat-tree are 1,152^2
+        switch demands)."""
+        got = self._all_pairs_loads(
+            lambda ex, sv, dv, w: self._switch_pair_loads(ex, sv, dv, w, route), LinkLoads)
+        if got is None:
+            macs = list(self.hosts)
+            return self.link_loads([(a, b) for a in macs for b in macs if a != b], None, route)
+        return got
 
     def mpi_link_loads(self, rank_to_mac, traffic=None, route="default"):
         """:meth:`link_loads` of an MPI job: ``traffic`` = {(src_rank,
         dst_rank): weight} between the ranks of ``rank_to_mac`` (a rank the
         map lacks is an unknown host); None: every ordered rank pair i != j
         with weight 1 -- the pairs of :meth:`mpi_flow_entries`."""
-        if traffic is None:
-            ranks = sorted(rank_to_mac)
-            pairs = [(rank_to_mac[a], rank_to_mac[b]) for a in ranks for b in ranks if a != b]
-            return self.link_loads(pairs, None, route)
-        items = [(k, x) for k, x in traffic.items() if k[0] in rank_to_mac and k[1] in rank_to_mac]
-        pairs = [(rank_to_mac[a], rank_to_mac[b]) for (a, b), _ in items]
-        return self.link_loads(pairs, [x for _, x in items], route)
+        pairs, weights = self._rank_pairs(rank_to_mac, traffic)
+        return self.link_loads(pairs, weights, route)
+
+    # -- predicted link loads under ECMP ----------------------------------
+    def _switch_pair_ecmp_loads(self, ex, sv, dv, w, split):
+        """(load float64 [E], reach bool [n]) of switch pairs (dense ids sv ->
+        dv, weights w u64) split over every shortest route: one
+        sdnr_ecmp_link_loads call per budget-sized chunk of destination rows,
+        over the pool's distance plane as it is (rows without pairs are
+        skipped by the kernel)."""
+        if split not in ("route", "hop"):
+            raise ValueError("split must be 'route' or 'hop'")
+        E = int(ex.csr.E)
+        load = np.zeros(E, np.float64)
+        reach = np.zeros(sv.shape[0], bool)
+        if sv.size == 0:
+            return load, reach
+        c = self._cache
+        store = c.sp
+        want = sorted(set(dv.tolist()))
+        batch = self._host_vertices(ex) if self._batch else ()
+        step = max(1, store.cap() - 1) if store.row_bytes else len(want)
+        for c0 in range(0, len(want), step):      # a budget's worth of rows at a time
+            chunk = want[c0:c0 + step]
+            tabs = c.sp_rows(self.engine, chunk, batch if c0 == 0 else ())
+            mine = np.nonzero(np.isin(dv, np.asarray(chunk, np.int64)))[0]
+            slots = np.asarray([store.row[v] for v in dv[mine].tolist()], np.int64)
+            # the distance plane holds -1 (u16 0xFFFF as int16) where unreached
+            reach[mine] = _gather(tabs[0], slots, sv[mine]) != -1
+            load += self.engine.ecmp_link_loads(ex, tabs[0], slots, sv[mine], w[mine], split)
+        return load, reach
+
+    def ecmp_link_loads(self, pairs, weights=None, split="route"):
+        """How much traffic crosses each link when every (src_mac, dst_mac)
+        pair of ``pairs`` spreads ``weights[i]`` (non-negative ints; None: 1
+        each) over ALL its shortest routes -- ECMP, what fat-trees,
+        dragonflies and Jellyfish are sized for -- as a
+        :class:`SplitLinkLoads`.
+
+        Defining property: ``ecmp_link_loads(pairs, w).as_dict()[(dpid,
+        port)]`` is the sum over i of ``w[i] / N_i`` times the number of
+        routes in ``find_route(*pairs[i], multiple=True)`` that hold that
+        entry, where N_i is the number of those routes (``split="route"``: a
+        controller choosing uniformly among the routes).  ``split="hop"``
+        instead halves, thirds, ... the traffic at every switch over its next
+        hops (an OpenFlow select group per switch); the two differ where the
+        routes are not spread evenly over the next hops.  Unknown hosts and
+        unreachable pairs contribute nothing; repeated pairs add.  No route
+        is enumerated and no count saturates (ecmp_loads.hip pushes the
+        demand down the shortest-path DAG of each destination, O(links) per
+        destination switch); link loads are float64 sums, equal to the
+        definition within rounding (not bit-reproducible between runs), the
+        last hops exact uint64."""
+        return self._pair_loads(
+            pairs, weights,
+            lambda ex, sv, dv, w: self._switch_pair_ecmp_loads(ex, sv, dv, w, split),
+            SplitLinkLoads)
+
+    def all_pairs_ecmp_link_loads(self, split="route"):
+        """:meth:`ecmp_link_loads` over every ordered pair of distinct hosts
+        with weight 1, from the per-switch host counts (as
+        :meth:`all_pairs_link_loads`)."""
+        got = self._all_pairs_loads(
+            lambda ex, sv, dv, w: self._switch_pair_ecmp_loads(ex, sv, dv, w, split),
+            SplitLinkLoads)
+        if got is None:
+            macs = list(self.hosts)
+            return self.ecmp_link_loads([(a, b) for a in macs for b in macs if a != b], None,
+                                        split)
+        return got
+
+    def mpi_ecmp_link_loads(self, rank_to_mac, traffic=None, split="route"):
+        """:meth:`ecmp_link_loads` of an MPI job (``traffic`` as in
+        :meth:`mpi_link_loads`)."""
+        pairs, weights = self._rank_pairs(rank_to_mac, traffic)
+        return self.ecmp_link_loads(pairs, weights, split)
 
     def find_routes(self, pairs, multiple=False):
         """find_route over many (src_mac, dst_mac) pairs; tables are computed
