@@ -56,6 +56,7 @@ extern "C" {
 #define SDNR_UNREACHED (-1)
 #define SDNR_DIST_INF  0xFFFFu
 #define SDNR_TREE_NONE 0xFFFFFFFFu
+#define SDNR_COST_INF 0xFFFFFFFFu /* sdnr_cost_tables: no route */
 
 typedef struct sdnr_ctx sdnr_ctx;
 
@@ -219,6 +220,44 @@ int sdnr_dfs_rows_affected(sdnr_ctx *ctx, const uint32_t *tree, const void *dept
 int sdnr_shortest_tables(sdnr_ctx *ctx, const int32_t *dst, int32_t ndst,
                          uint16_t *dist, int32_t *nh, int32_t *nh_port,
                          uint32_t flags);
+
+/* Per-link costs of the uploaded graph (OSPF / IS-IS style metrics: cost a hot
+ * link up, cost a link out for maintenance, prefer the fast links): cost[e] is
+ * the cost of the e-th directed link in the uploaded CSR's edge order, E
+ * entries in a HOST buffer, copied to the context's primary device.  Checked
+ * on the host: every cost >= 1 (a zero would allow cost-neutral cycles) and,
+ * with cmax = the largest, cmax * (V - 1) < 0xFFFFFFFF, so no path sum reaches
+ * SDNR_COST_INF; else SDNR_ERR_INVAL and the costs in force stay.  NULL clears
+ * the costs, and so does sdnr_graph_upload (the edge order changes).  Only
+ * sdnr_cost_tables reads them: every other entry point counts hops as before. */
+int sdnr_graph_costs(sdnr_ctx *ctx, const uint32_t *cost);
+
+/* Least-cost routes under the uploaded link costs, as per-destination tables
+ * (the weighted counterpart of sdnr_shortest_tables): for every destination
+ * dst[i] and every vertex x
+ *   pcost[i*V+x]    least sum of link costs over the paths x -> dst[i] (0 at
+ *                   dst[i], SDNR_COST_INF if there is none),
+ *   nh[i*V+x]       smallest out-neighbour n with cost(x -> n) + pcost(n) ==
+ *                   pcost(x) (-1 for x == dst[i] or unreachable),
+ *   nh_port[i*V+x]  links[x][nh].src.port_no.
+ * Following nh from x gives the lexicographically smallest least-cost route
+ * (sdnr_shortest_tables' tie rule); costs are positive, so an nh row is an
+ * in-tree toward dst[i] and sdnr_link_loads with SDNR_LOADS_TO_ROOT takes it
+ * as it is.  With every cost 1 the tables equal sdnr_shortest_tables' (dist
+ * widened to u32, SDNR_DIST_INF -> SDNR_COST_INF).  nh and nh_port go together
+ * and may both be NULL (costs only).  Everything is integer and bit-exact.
+ * Host buffers: synchronous; SDNR_DEVICE_PTRS: asynchronous on the context's
+ * stream; SDNR_TIMING as in sdnr_shortest_tables.  Without uploaded costs:
+ * SDNR_ERR_STATE.  A destination outside [0, V) is handled as
+ * sdnr_shortest_tables handles it: SDNR_ERR_INVAL for host buffers (the ids
+ * are checked before anything runs), an empty row (SDNR_COST_INF / -1) for
+ * device ids.  One launch (pull Bellman-Ford sweeps to the fixed point, at
+ * most V of them; a run that needed more is reported by sdnr_synchronize as
+ * SDNR_ERR_INVAL -- costs the upload check would have refused); on a
+ * multi-device context it runs on the primary device. */
+int sdnr_cost_tables(sdnr_ctx *ctx, const int32_t *dst, int32_t ndst,
+                     uint32_t *pcost, int32_t *nh, int32_t *nh_port,
+                     uint32_t flags);
 
 /* All-pairs hop distances by min-plus squaring (D <- min(D, D (x) D) until
  * stable) for small dense graphs: dist[i*V+j] = hops i -> j (SDNR_DIST_INF

@@ -61,6 +61,10 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "labelling of the uploaded graph (a vertex without a next hop, a "
                              "level >= V, a route count above the double range) or pair_off is "
                              "not monotone: loads invalid");
+        if (h & kErrCostTables)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_tables: V relaxation sweeps did not reach "
+                             "the fixed point (link costs outside what sdnr_graph_costs accepts): "
+                             "tables invalid");
         if (h & kErrLastPort)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_route_expand_packed: a last port outside "
                              "[0, 0xFFFF] (u32 entries hold 16-bit ports): entries invalid");
@@ -126,6 +130,9 @@ static void free_graph(sdnr_ctx *c)
         if (*b) (void)hipFree(*b);
         *b = nullptr;
     }
+    if (c->cost) (void)hipFree(c->cost);         // the costs follow the edge order
+    c->cost = nullptr;
+    c->has_cost = false;
     if (c->radj16 && c->radj_owned) (void)hipFree(c->radj16);
     if (c->runs) (void)hipFree(c->runs);
     c->runs = nullptr;
@@ -1187,6 +1194,69 @@ int sdnr_shortest_tables(sdnr_ctx *ctx, const int32_t *dst, int32_t ndst, uint16
     void *const out[3] = {dist, nh, nh_port};
     const size_t es[3] = {2, 4, 4};
     return run_sharded(ctx, dst, ndst, out, es, flags, shard_shortest);
+}
+
+int sdnr_graph_costs(sdnr_ctx *ctx, const uint32_t *cost)
+{
+    CHECK_CTX(ctx);
+    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_graph_costs: no graph uploaded");
+    const size_t E = (size_t)ctx->E;
+    if (cost) {
+        uint32_t cmax = 0;
+        for (size_t e = 0; e < E; ++e) {
+            if (cost[e] == 0)
+                return sdnr_fail(SDNR_ERR_INVAL, "sdnr_graph_costs: cost[%zu] is 0 (costs are "
+                                 ">= 1)", e);
+            if (cost[e] > cmax) cmax = cost[e];
+        }
+        const uint64_t worst = (uint64_t)cmax * (uint64_t)(ctx->V > 0 ? ctx->V - 1 : 0);
+        if (worst >= SDNR_COST_INF)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_graph_costs: largest cost %u * (V - 1 = %d) "
+                             "reaches SDNR_COST_INF", cmax, ctx->V - 1);
+    }
+    SDNR_HIP(hipSetDevice(ctx->device));
+    SDNR_HIP(hipStreamSynchronize(ctx->stream));         // a call may still read the old costs
+    if (ctx->cost) (void)hipFree(ctx->cost);
+    ctx->cost = nullptr;
+    ctx->has_cost = false;
+    if (!cost) return SDNR_OK;
+    SDNR_HIP(hipMalloc(reinterpret_cast<void **>(&ctx->cost), E ? E * sizeof(uint32_t) : 4));
+    if (E) SDNR_HIP(hipMemcpy(ctx->cost, cost, E * sizeof(uint32_t), hipMemcpyHostToDevice));
+    ctx->has_cost = true;
+    return SDNR_OK;
+}
+
+int sdnr_cost_tables(sdnr_ctx *ctx, const int32_t *dst, int32_t ndst, uint32_t *pcost,
+                     int32_t *nh, int32_t *nh_port, uint32_t flags)
+{
+    int rc = begin_call(ctx, ndst, dst, flags, "sdnr_cost_tables");
+    if (rc) return rc;
+    if (!ctx->has_cost)
+        return sdnr_fail(SDNR_ERR_STATE, "sdnr_cost_tables: no link costs uploaded for this "
+                         "graph (sdnr_graph_costs)");
+    if (ndst > 0 && !pcost) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_tables: null pcost");
+    if ((nh == nullptr) != (nh_port == nullptr))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_tables: nh and nh_port go together");
+    if (ndst == 0 || ctx->V == 0) return SDNR_OK;
+    if (flags & SDNR_DEVICE_PTRS) return sdnr_launch_cost_tables(ctx, dst, ndst, pcost, nh, nh_port);
+    // host buffers: stage the ids and the rows on the primary device
+    const size_t n = (size_t)ndst * (size_t)ctx->V * 4;
+    size_t need = 4 * (size_t)ndst + 256 + (n + 256) * (nh ? 3 : 1);
+    if ((rc = sdnr_reserve(&ctx->stage, &ctx->stage_bytes, need))) return rc;
+    Stage st{static_cast<char *>(ctx->stage)};
+    int32_t *d_ids = static_cast<int32_t *>(st.take(4 * (size_t)ndst));
+    uint32_t *d_pc = static_cast<uint32_t *>(st.take(n));
+    int32_t *d_nh = nh ? static_cast<int32_t *>(st.take(n)) : nullptr;
+    int32_t *d_np = nh ? static_cast<int32_t *>(st.take(n)) : nullptr;
+    SDNR_HIP(hipMemcpyAsync(d_ids, dst, 4 * (size_t)ndst, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = sdnr_launch_cost_tables(ctx, d_ids, ndst, d_pc, d_nh, d_np))) return rc;
+    SDNR_HIP(hipMemcpyAsync(pcost, d_pc, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (nh) {
+        SDNR_HIP(hipMemcpyAsync(nh, d_nh, n, hipMemcpyDeviceToHost, ctx->stream));
+        SDNR_HIP(hipMemcpyAsync(nh_port, d_np, n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SDNR_HIP(hipStreamSynchronize(ctx->stream));
+    return sdnr_check_watchdog(ctx);
 }
 
 int sdnr_apsp(sdnr_ctx *ctx, uint16_t *dist, uint32_t flags)

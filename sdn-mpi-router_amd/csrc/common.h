@@ -53,6 +53,8 @@ struct sdnr_ctx {
     int32_t max_indeg = 0x7FFFFFFF;     // maximum in-degree (set with adj16/radj16)
     int32_t W = 0;                      // ELL row width (0: CSR only)
     int32_t *row_ptr = nullptr, *col = nullptr, *port = nullptr;
+    uint32_t *cost = nullptr;           // per-link costs in edge order (sdnr_graph_costs)
+    bool has_cost = false;              // costs uploaded for this graph (E may be 0)
     int32_t *ell_col = nullptr, *ell_port = nullptr;
     uint16_t *ell16 = nullptr;          // ELL ids as u16 (low 16 bits when V > 65535), 0xFFFF pad
     uint32_t *ell_hi = nullptr;         // per row: the 17th id bit of each slot (65535 <= V < 131071)
@@ -178,6 +180,15 @@ constexpr int kErrEcmpLoads = 8192; // sdnr_ecmp_link_loads: a dist row is no BF
 // else the counts and flows in global scratch (16 bytes per vertex and
 // workgroup, at most kLoadsScratchBytes in all)
 constexpr int kEcmpLoadsLdsMaxV = 9000;
+constexpr int kErrCostTables = 16384; // sdnr_cost_tables: V sweeps did not reach the fixed point
+
+// sdnr_cost_tables keeps the least-cost rows of a batch of destinations in
+// LDS: 8 of them (32 bytes per vertex) up to kCostLdsMaxV8 vertices, 4 (16
+// bytes per vertex) up to kCostLdsMaxV -- 160,000 of the CU's 163,840 bytes at
+// either cap --, else 4 in global scratch (16 bytes per vertex and workgroup,
+// at most kLoadsScratchBytes in all)
+constexpr int kCostLdsMaxV8 = 5000;
+constexpr int kCostLdsMaxV = 10000;
 
 // error plumbing (capi.hip)
 int sdnr_fail(int code, const char *fmt, ...);
@@ -251,5 +262,8 @@ int sdnr_launch_ecmp_link_loads(sdnr_ctx *ctx, const uint16_t *d_dist, int32_t n
                                 const int64_t *d_pair_off, int64_t pair_lo, int64_t pair_hi,
                                 const int32_t *d_srcs, const uint64_t *d_weight, double *d_load,
                                 bool hop);
+// least-cost tables under the uploaded per-link costs (cost_tables.hip)
+int sdnr_launch_cost_tables(sdnr_ctx *ctx, const int32_t *d_dst, int32_t ndst, uint32_t *d_pcost,
+                            int32_t *d_nh, int32_t *d_nh_port);
 int sdnr_launch_edge_ports(sdnr_ctx *ctx, const uint64_t *d_ends, int32_t nends,
                            const uint64_t *d_ports, int32_t nports, uint8_t *d_is_edge);

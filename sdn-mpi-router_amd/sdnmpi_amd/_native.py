@@ -30,6 +30,7 @@ LOADS_SPLIT_HOP = 0x10   # sdnr_ecmp_link_loads: even split over a switch's next
 UNREACHED = -1
 DIST_INF = 0xFFFF
 TREE_NONE = 0xFFFFFFFF
+COST_INF = 0xFFFFFFFF    # sdnr_cost_tables: no route
 TREE_INT32 = 0           # int32 parents (sdnr_dfs_rows_affected)
 TREE_PORT16 = 1          # parent | port << 16 (sdnr_dfs_tables_packed)
 TREE_SLOT = 2            # parent | slot << 26 (sdnr_dfs_tables_slots)
@@ -45,7 +46,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_ecmp_routes",
     "sdnr_last_kernel_ms", "sdnr_last_kernel", "sdnr_last_launches", "sdnr_last_sweeps",
     "sdnr_edge_ports", "sdnr_dfs_rows_affected", "sdnr_link_loads",
-    "sdnr_ecmp_link_loads",
+    "sdnr_ecmp_link_loads", "sdnr_graph_costs", "sdnr_cost_tables",
 )
 
 
@@ -103,6 +104,8 @@ def _bind(L):
         "sdnr_dfs_rows_affected": ([vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, u32], c_int),
         "sdnr_link_loads": ([vp, vp, i32, i32, vp, vp, vp, vp, u32], c_int),
         "sdnr_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, vp, u32], c_int),
+        "sdnr_graph_costs": ([vp, vp], c_int),
+        "sdnr_cost_tables": ([vp, vp, i32, vp, vp, vp, u32], c_int),
     }
     # an A/B build named by SDNROUTE_LIB may predate some entry points: those
     # stay unbound (calling one raises AttributeError); the in-tree library
@@ -315,6 +318,30 @@ class Context(object):
                                               _ptr(nh), _ptr(nhp), 0))
         return dist, nh, nhp
 
+    def set_link_costs(self, cost):
+        """Per-link costs of the uploaded graph (uint32 [E], CSR edge order,
+        every one >= 1; None clears them): sdnr_graph_costs.  A new upload
+        clears them too."""
+        if cost is None:
+            _check(self._lib.sdnr_graph_costs(self._h, None))
+            return
+        c = np.ascontiguousarray(cost, np.uint32)
+        if c.shape != (self.E,):
+            raise ValueError("one cost per link of the uploaded graph (%d)" % self.E)
+        _check(self._lib.sdnr_graph_costs(self._h, _ptr(c)))
+
+    def cost_tables(self, dsts, with_nexthop=True):
+        """Least-cost tables under the uploaded costs: (pcost uint32 [D, V],
+        nh, nh_port int32 or None), see sdnr_cost_tables."""
+        dsts = np.ascontiguousarray(dsts, np.int32)
+        D, V = int(dsts.shape[0]), self.V
+        pcost = np.empty((D, V), np.uint32)
+        nh = np.empty((D, V), np.int32) if with_nexthop else None
+        nhp = np.empty((D, V), np.int32) if with_nexthop else None
+        _check(self._lib.sdnr_cost_tables(self._h, _ptr(dsts), D, _ptr(pcost), _ptr(nh),
+                                          _ptr(nhp), 0))
+        return pcost, nh, nhp
+
     def expand_routes(self, parent, port, hops, rows, dsts, last_port):
         """Flow entries of many pairs from host tables: (offsets int64
         [n+1], hop_switch int32, hop_port int32); see sdnr_route_expand."""
@@ -508,6 +535,16 @@ class Context(object):
         flags = DEVICE_PTRS | (TIMING if timing else 0)
         _check(self._lib.sdnr_shortest_tables(
             self._h, ctypes.c_void_p(dst_ptr), int(ndst), ctypes.c_void_p(dist_ptr),
+            ctypes.c_void_p(nh_ptr) if nh_ptr else None,
+            ctypes.c_void_p(nh_port_ptr) if nh_port_ptr else None, flags))
+
+    def cost_tables_device(self, dst_ptr, ndst, pcost_ptr, nh_ptr=0, nh_port_ptr=0,
+                           timing=False):
+        """sdnr_cost_tables over device buffers (pcost u32, nh / nh_port int32
+        [ndst][V]; both next-hop pointers or neither), asynchronous."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0)
+        _check(self._lib.sdnr_cost_tables(
+            self._h, ctypes.c_void_p(dst_ptr), int(ndst), ctypes.c_void_p(pcost_ptr),
             ctypes.c_void_p(nh_ptr) if nh_ptr else None,
             ctypes.c_void_p(nh_port_ptr) if nh_port_ptr else None, flags))
 

@@ -41,7 +41,8 @@ from .graph import empty_csr
 
 __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "shortest_paths_lex", "count_shortest_paths", "ECMP_LIMIT", "DEFAULT_TABLE_BUDGET", "tree_layout", "dfs_row_bytes",
-           "sp_row_bytes", "link_loads_host", "ecmp_link_loads_host"]
+           "sp_row_bytes", "link_loads_host", "ecmp_link_loads_host", "cost_tables_host",
+           "check_link_costs", "COST_INF", "COST_MAX", "COST_LDS_MAX_V", "COST_LDS_B8_MAX_V"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -397,6 +398,85 @@ def ecmp_link_loads_host(csr, dist, rows, srcs, weights=None, split="route"):
     return load
 
 
+COST_INF = _native.COST_INF
+COST_MAX = COST_INF - 1         # the largest link cost (on a two-switch fabric)
+COST_LDS_MAX_V = 10000          # csrc/common.h kCostLdsMaxV: cost rows in LDS up to this V
+COST_LDS_B8_MAX_V = 5000        # ... kCostLdsMaxV8: in batches of 8 destinations up to this V
+
+
+def check_link_costs(csr, cost):
+    """The link costs as uint32 [E], after sdnr_graph_costs' checks: one per
+    link, every one >= 1, the largest times (V - 1) below COST_INF."""
+    c = np.asarray(cost)
+    if c.shape != (int(csr.E),):
+        raise ValueError("one cost per link of the graph (%d)" % int(csr.E))
+    if c.size:
+        if c.dtype.kind not in "iu":
+            raise ValueError("link costs are integers")
+        lo, hi = int(c.min()), int(c.max())
+        if lo < 1:
+            raise ValueError("link costs are >= 1")
+        if hi * max(0, int(csr.V) - 1) >= COST_INF:
+            raise ValueError("largest cost %d * (V - 1) reaches COST_INF" % hi)
+    return c.astype(np.uint32)
+
+
+def cost_tables_host(csr, cost, dsts):
+    """CPU restatement of sdnr_cost_tables (the CPU tests' engine double and
+    the checker of cost_tables.hip): (pcost uint32 [D, V], nh int32, nh_port
+    int32) of the least-cost routes toward each destination of ``dsts`` under
+    the per-link costs ``cost`` (uint32 [E], CSR edge order).
+
+    Deliberately not the kernel's algorithm: one Dijkstra per destination on
+    the reversed graph (``heapq``, Python ints), then the next-hop scan --
+    the first entry of x's ascending row with cost + pcost[n] == pcost[x]."""
+    import heapq
+    V, E = int(csr.V), int(csr.E)
+    cost = check_link_costs(csr, cost)
+    rp = np.asarray(csr.row_ptr, np.int64)
+    col = np.asarray(csr.col, np.int64)
+    port = np.asarray(csr.port, np.int32)
+    esrc = np.repeat(np.arange(V, dtype=np.int64), np.diff(rp))
+    # reversed graph: in-links of every vertex
+    order = np.argsort(col, kind="stable")
+    rrp = np.zeros(V + 1, np.int64)
+    np.cumsum(np.bincount(col, minlength=V), out=rrp[1:])
+    rsrc = esrc[order].tolist()
+    rcost = cost[order].tolist()
+    rrp_l = rrp.tolist()
+    dsts = np.asarray(dsts, np.int64)
+    D = int(dsts.shape[0])
+    pcost = np.full((D, V), COST_INF, np.uint32)
+    nh = np.full((D, V), -1, np.int32)
+    nhp = np.full((D, V), -1, np.int32)
+    c64 = cost.astype(np.int64)
+    for i, d in enumerate(dsts.tolist()):
+        if d < 0 or d >= V:
+            continue                                       # unknown destination: empty row
+        best = [None] * V
+        best[d] = 0
+        heap = [(0, d)]
+        while heap:
+            c, n = heapq.heappop(heap)
+            if c != best[n]:
+                continue
+            for k in range(rrp_l[n], rrp_l[n + 1]):
+                x, t = rsrc[k], c + rcost[k]
+                if best[x] is None or t < best[x]:
+                    best[x] = t
+                    heapq.heappush(heap, (t, x))
+        pc = np.array([-1 if b is None else b for b in best], np.int64)
+        pcost[i] = np.where(pc < 0, COST_INF, pc).astype(np.uint32)
+        if E:
+            # links on a least-cost route; the first of each row (CSR order)
+            on = (pc[col] >= 0) & (pc[esrc] > 0) & (c64 + pc[col] == pc[esrc])
+            e = np.nonzero(on)[0]
+            x, first = np.unique(esrc[e], return_index=True)
+            nh[i, x] = col[e[first]]
+            nhp[i, x] = port[e[first]]
+    return pcost, nh, nhp
+
+
 class RouteEngine(object):
     """The GPU route engine of one TopologyDB: HIP device ``device`` (int),
     or the devices of a list (single-process multi-GPU, sources sharded over
@@ -411,6 +491,7 @@ class RouteEngine(object):
         self._loaded = None
         self._csr_dev = None        # (export, row_ptr int64, port int32) on the device
         self._keys_dev = None       # (export, edge keys int64, port int32) on the device
+        self._costs = None          # (export, link costs uint32) in force on the context
 
     # -- plumbing -------------------------------------------------------
     def _ready(self):
@@ -428,6 +509,7 @@ class RouteEngine(object):
         if self._loaded is not export:
             self.ctx.upload(export.csr if export.csr.V else empty_csr())
             self._loaded = export
+            self._costs = None          # an upload clears the context's link costs
 
     def csr_device(self, export):
         """(row_ptr int64, port int32) of the export on the device (slot trees
@@ -519,6 +601,36 @@ class RouteEngine(object):
                                             nhp.data_ptr())
             self.ctx.synchronize()
         return dist, nh, nhp
+
+    def set_link_costs(self, export, cost):
+        """Upload the per-link costs (uint32 [E], the export's CSR edge
+        order) unless they are the ones in force for this export."""
+        self.load(export)
+        cost = check_link_costs(export.csr, cost)
+        cur = self._costs
+        if cur is None or cur[0] is not export or not np.array_equal(cur[1], cost):
+            self._costs = None
+            self.ctx.set_link_costs(cost)
+            self._costs = (export, cost.copy())
+
+    def cost_tables(self, export, cost, dsts, timing=False):
+        """Least-cost tables under per-link costs (cost_tables.hip,
+        sdnr_cost_tables): (pcost int32 [D, V] holding u32 -- -1 is COST_INF,
+        no route --, nh, nh_port int32) on the device, as ``shortest_tables``
+        returns its tables."""
+        self.set_link_costs(export, cost)
+        t = self._torch
+        D, V = len(dsts), export.csr.V
+        pcost = self._empty(D, V, t.int32)
+        nh = self._empty(D, V, t.int32)
+        nhp = self._empty(D, V, t.int32)
+        if D and V:
+            td = self._ids(dsts)
+            self._ready()
+            self.ctx.cost_tables_device(td.data_ptr(), D, pcost.data_ptr(), nh.data_ptr(),
+                                        nhp.data_ptr(), timing=timing)
+            self.ctx.synchronize()          # also raises on a tripped sweep bound
+        return pcost, nh, nhp
 
     def ecmp(self, export, dist, rows, srcs):
         """Every shortest route of each (rows[i], srcs[i]) pair, lexicographic

@@ -26,8 +26,8 @@ first route query raises (``sdnmpi_amd._native.NativeUnavailable`` /
 
 import numpy as np
 
-from ..engine import (INT32, RouteEngine, TableCache, _gather, _host, _take, _torch, _u16,
-                      shortest_paths_lex, tree_path)
+from ..engine import (COST_MAX, DEFAULT_TABLE_BUDGET, INT32, RouteEngine, TableCache, _gather,
+                      _host, _take, _torch, _u16, check_link_costs, shortest_paths_lex, tree_path)
 from ..graph import TrackedDict, Versions, export_graph, update_export
 from ..incremental import edge_diff
 
@@ -160,6 +160,10 @@ class TopologyDB(object):
         self._export = None
         self._cache = None
         self._em = (None, None, None)    # (links/switches version, edge-port state, export)
+        self._link_costs = {}            # (src dpid, dst dpid) -> cost (operator configuration)
+        self._cost_version = 0
+        self._cost_vec = None            # (export, cost version, uint32 [E] costs)
+        self._cost_memo = None           # least-cost rows per destination (_cost_rows)
         # Switch DPID -> Switch; src DPID -> dst DPID -> Link; MAC -> Host
         self.switches = {}
         self.links = {}
@@ -848,6 +852,221 @@ class TopologyDB(object):
         :meth:`mpi_link_loads`)."""
         pairs, weights = self._rank_pairs(rank_to_mac, traffic)
         return self.ecmp_link_loads(pairs, weights, split)
+
+    # -- link costs and least-cost routes ---------------------------------
+    def set_link_cost(self, src_dpid, dst_dpid, cost):
+        """Cost of the directed link src_dpid -> dst_dpid for the least-cost
+        routes (an OSPF / IS-IS style metric; default 1): an int in
+        [1, 2**32 - 2], else ValueError.  Operator configuration, kept by dpid
+        pair independently of ``links``: it applies whenever that link
+        exists, so a flapping link keeps its cost.  ``find_route``,
+        ``route_tables`` and the hop-count load methods ignore costs."""
+        self.set_link_costs({(src_dpid, dst_dpid): cost})
+
+    def set_link_costs(self, mapping):
+        """:meth:`set_link_cost` for every {(src_dpid, dst_dpid): cost} of
+        ``mapping``; nothing is set when one of them is refused."""
+        items = list(dict(mapping).items())
+        for k, c in items:
+            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or \
+                    not 1 <= int(c) <= COST_MAX:
+                raise ValueError("link cost of %r must be an int in [1, 2**32 - 2]: %r" % (k, c))
+            if not isinstance(k, tuple) or len(k) != 2:
+                raise ValueError("link costs are keyed by (src_dpid, dst_dpid): %r" % (k,))
+        for k, c in items:
+            self._link_costs[(k[0], k[1])] = int(c)
+        self._cost_version += 1
+
+    def link_cost(self, src_dpid, dst_dpid):
+        """The cost set for src_dpid -> dst_dpid (1 when none was)."""
+        return self._link_costs.get((src_dpid, dst_dpid), 1)
+
+    def clear_link_costs(self):
+        """Every link back to cost 1."""
+        self._link_costs.clear()
+        self._cost_version += 1
+
+    def _cost_vector(self, ex):
+        """uint32 [E]: the cost of every link of the export, CSR edge order."""
+        got = self._cost_vec
+        if got is not None and got[0] is ex and got[1] == self._cost_version:
+            return got[2]
+        csr = ex.csr
+        cost = np.ones(int(csr.E), np.uint32)
+        rp, col = csr.row_ptr, csr.col
+        for (a, b), c in self._link_costs.items():
+            u, v = ex.index.get(a), ex.index.get(b)
+            if u is None or v is None:
+                continue
+            lo, hi = int(rp[u]), int(rp[u + 1])
+            e = lo + int(np.searchsorted(col[lo:hi], v))
+            if e < hi and int(col[e]) == v:
+                cost[e] = c
+        check_link_costs(csr, cost)      # the largest cost * (V - 1) stays below COST_INF
+        self._cost_vec = (ex, self._cost_version, cost)
+        return cost
+
+    def _cost_rows(self, ex, want):
+        """Memo of least-cost rows holding every destination of ``want`` (at
+        most :meth:`_cost_cap` of them): dict(slot {destination: row}, pcost,
+        nh, nh_port [n, V] tables as the engine returned them).  Rows are kept
+        per destination until the graph or the costs change, or the table
+        budget is exceeded; then the memo is dropped wholesale."""
+        m = self._cost_memo
+        if m is None or m["ex"] is not ex or m["version"] != self._cost_version:
+            m = self._cost_memo = {"ex": ex, "version": self._cost_version, "slot": {},
+                                   "tabs": None}
+        new = [d for d in want if d not in m["slot"]]
+        if not new:
+            return m
+        if len(m["slot"]) + len(new) > self._cost_cap(ex):
+            m["slot"], m["tabs"] = {}, None
+            new = list(want)
+        tabs = tuple(self.engine.cost_tables(ex, self._cost_vector(ex), new))
+        if isinstance(tabs[0], np.ndarray):         # u32 costs are held as int32: COST_INF is -1
+            tabs = (np.ascontiguousarray(tabs[0], np.uint32).view(np.int32),) + tabs[1:]
+        base = len(m["slot"])
+        if m["tabs"] is None:
+            m["tabs"] = tuple(tabs)
+        elif isinstance(tabs[0], np.ndarray):
+            m["tabs"] = tuple(np.concatenate([a, b]) for a, b in zip(m["tabs"], tabs))
+        else:
+            m["tabs"] = tuple(_torch().cat([a, b]) for a, b in zip(m["tabs"], tabs))
+        for k, d in enumerate(new):
+            m["slot"][d] = base + k
+        return m
+
+    def _cost_cap(self, ex):
+        """Least-cost rows (12 bytes per vertex) the table budget holds."""
+        budget = DEFAULT_TABLE_BUDGET if self._budget is None else self._budget
+        return max(1, int(budget) // max(1, 12 * int(ex.csr.V)))
+
+    def least_cost_tables(self, vertices=None):
+        """Per-destination tables of the least-cost routes under the link
+        costs (:meth:`set_link_cost`; cost_tables.hip) for every host-bearing
+        switch, or the dense ``vertices`` given: dict(destinations, pcost
+        uint32 [n, V] -- ``COST_INF`` 0xFFFFFFFF where there is no route --,
+        nh, nh_port int32, dpids).  Following ``nh`` gives the
+        lexicographically smallest least-cost route; with no cost set the
+        tables are ``route_tables("shortest")``'s."""
+        ex = self.graph()
+        hv = self._host_vertices(ex) if vertices is None else [int(v) for v in vertices]
+        V, n = int(ex.csr.V), len(hv)
+        pcost = np.empty((n, V), np.uint32)
+        nh = np.empty((n, V), np.int32)
+        nhp = np.empty((n, V), np.int32)
+        step = self._cost_cap(ex)
+        for i in range(0, n, step):                 # a budget's worth of rows at a time
+            chunk = hv[i:i + step]
+            m = self._cost_rows(ex, sorted(set(chunk)))
+            idx = np.asarray([m["slot"][v] for v in chunk], np.int64)
+            p, a, b = (_host(_take(t, idx)) for t in m["tabs"])
+            pcost[i:i + len(chunk)] = p.view(np.uint32)
+            nh[i:i + len(chunk)] = a
+            nhp[i:i + len(chunk)] = b
+        return {"destinations": np.asarray(hv, np.int32), "pcost": pcost, "nh": nh,
+                "nh_port": nhp, "dpids": ex.csr.dpids}
+
+    def _least_cost_fdb(self, ex, s, d, last, rows):
+        """fdb of the route that follows the next-hop row ``rows`` = (pcost,
+        nh, nh_port host rows of destination d) from s; [] without a route."""
+        pc, nh, nhp = rows
+        if s != d and int(pc[s]) == -1:
+            return []
+        out, x, dpids = [], s, ex.csr.dpids
+        while x != d:
+            out.append((int(dpids[x]), int(nhp[x])))
+            x = int(nh[x])
+            if x < 0 or len(out) > int(ex.csr.V):
+                raise RuntimeError("least-cost next-hop row is not an in-tree")
+        out.append(last)
+        return out
+
+    def find_route_least_cost(self, src_mac, dst_mac):
+        """The least-cost route between two hosts (or switch-local ports)
+        under the link costs, in ``find_route``'s format and with its endpoint
+        rules: [] for an unknown MAC or an unreachable destination, the one
+        last-hop entry for two endpoints on one switch.  Among equal-cost
+        routes the lexicographically smallest dpid sequence, the tie rule of
+        ``find_route(multiple=True)[0]`` -- which it equals while every cost
+        is 1."""
+        return self.find_routes_least_cost([(src_mac, dst_mac)])[0]
+
+    def find_routes_least_cost(self, pairs):
+        """:meth:`find_route_least_cost` over many (src_mac, dst_mac) pairs;
+        the destination rows are computed once for all of them."""
+        pairs = list(pairs)
+        ex = self.graph()
+        out = [[] for _ in pairs]
+        ends = {}
+        for i, (a, b) in enumerate(pairs):
+            ea, eb = self._endpoint(a), self._endpoint(b)
+            if ea is None or eb is None:
+                continue
+            ends[i] = (ex.index[ea[0]], ex.index[eb[0]], self._last_hop(eb[0], eb[1], b))
+        want = sorted(set(e[1] for e in ends.values()))
+        step = self._cost_cap(ex)
+        for c0 in range(0, len(want), step):        # a budget's worth of rows at a time
+            chunk = want[c0:c0 + step]
+            m = self._cost_rows(ex, chunk)
+            idx = np.asarray([m["slot"][d] for d in chunk], np.int64)
+            host = [_host(_take(t, idx)) for t in m["tabs"]]
+            at = {d: k for k, d in enumerate(chunk)}
+            for i, (s, d, last) in ends.items():
+                if d in at:
+                    k = at[d]
+                    out[i] = self._least_cost_fdb(ex, s, d, last,
+                                                  (host[0][k].view(np.int32), host[1][k],
+                                                   host[2][k]))
+        return out
+
+    def _switch_pair_cost_loads(self, ex, sv, dv, w):
+        """(load uint64 [E], reach bool [n]) of switch pairs (dense ids sv ->
+        dv, weights w u64) on their least-cost routes: sdnr_link_loads with
+        SDNR_LOADS_TO_ROOT over the least-cost next-hop rows, a budget-sized
+        chunk of destination rows at a time."""
+        E = int(ex.csr.E)
+        load = np.zeros(E, np.uint64)
+        reach = np.zeros(sv.shape[0], bool)
+        if sv.size == 0:
+            return load, reach
+        want = sorted(set(dv.tolist()))
+        step = self._cost_cap(ex)
+        for c0 in range(0, len(want), step):
+            chunk = want[c0:c0 + step]
+            m = self._cost_rows(ex, chunk)
+            mine = np.nonzero(np.isin(dv, np.asarray(chunk, np.int64)))[0]
+            slots = np.asarray([m["slot"][v] for v in dv[mine].tolist()], np.int64)
+            pc, nh = m["tabs"][0], m["tabs"][1]
+            # pcost is held as int32: COST_INF reads -1
+            reach[mine] = _gather(pc, slots, sv[mine]) != -1
+            urows, inv = np.unique(slots, return_inverse=True)
+            load += self.engine.link_loads(ex, _take(nh, urows), INT32, inv, sv[mine], w[mine],
+                                           to_root=True)
+        return load, reach
+
+    def least_cost_link_loads(self, pairs, weights=None):
+        """:meth:`link_loads` with every pair on its least-cost route
+        (:meth:`find_route_least_cost`) -- what the links would carry after
+        the costs were changed: ``as_dict()`` is the weighted count of the
+        ``(dpid, out_port)`` entries of those routes.  Exact uint64 sums."""
+        return self._pair_loads(pairs, weights, self._switch_pair_cost_loads, LinkLoads)
+
+    def all_pairs_least_cost_link_loads(self):
+        """:meth:`least_cost_link_loads` over every ordered pair of distinct
+        hosts with weight 1, from the per-switch host counts (as
+        :meth:`all_pairs_link_loads`)."""
+        got = self._all_pairs_loads(self._switch_pair_cost_loads, LinkLoads)
+        if got is None:
+            macs = list(self.hosts)
+            return self.least_cost_link_loads([(a, b) for a in macs for b in macs if a != b])
+        return got
+
+    def mpi_least_cost_link_loads(self, rank_to_mac, traffic=None):
+        """:meth:`least_cost_link_loads` of an MPI job (``traffic`` as in
+        :meth:`mpi_link_loads`)."""
+        pairs, weights = self._rank_pairs(rank_to_mac, traffic)
+        return self.least_cost_link_loads(pairs, weights)
 
     def find_routes(self, pairs, multiple=False):
         """find_route over many (src_mac, dst_mac) pairs; tables are computed
