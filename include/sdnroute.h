@@ -394,6 +394,44 @@ int sdnr_ecmp_link_loads(sdnr_ctx *ctx, const uint16_t *dist, int32_t nrows,
                          const int64_t *pair_off, const int32_t *srcs, const uint64_t *weight,
                          double *load, uint32_t flags);
 
+/* Per-link loads of a traffic matrix under ECMP over the LEAST-COST routes:
+ * sdnr_ecmp_link_loads under the uploaded link costs (sdnr_graph_costs), what
+ * an OSPF / IS-IS fabric with equal-cost multipath carries once links are
+ * costed up or out -- where sdnr_link_loads over sdnr_cost_tables' nh rows puts
+ * each pair on the one lexicographically smallest route.
+ *   pcost     [nrows][V] u32 rows as sdnr_cost_tables writes them, row r = the
+ *             least path costs toward one destination (SDNR_COST_INF: no route);
+ *   pair_off, srcs, weight, load: as in sdnr_ecmp_link_loads.  The call ADDS
+ *             into load.
+ * Link e = (x -> n) is a next-hop link of x when pcost[n] != SDNR_COST_INF and
+ * pcost[n] + cost[e] == pcost[x]; costs are >= 1, so these links form a DAG
+ * toward the destination, but the next hops of a vertex need not sit one hop
+ * count down (a direct link of cost 2 ties two links of cost 1): the vertices
+ * are ordered by their longest next-hop chain: pull sweeps finalise the
+ * vertices of chain length 1, 2, ... together with their route counts sigma[]
+ * (double), and the demand is pushed down that order, O(E) per row for the
+ * push and at most O(E) per sweep.  Default (route split): each of the
+ * pair's sigma[s] least-cost routes carries w / sigma[s].
+ * SDNR_LOADS_SPLIT_HOP: every switch sends 1 / (number of its next hops) over
+ * each.  Unreachable sources, sources outside [0, V), the pair s == d and zero
+ * weights contribute nothing; repeated pairs add.  Sums are f64 atomics: every
+ * term is non-negative, but the last bits depend on the order of arrival and
+ * may differ between runs unless every partial sum is exact (power-of-two
+ * shares, integer weights).  No NaN or Inf reaches load.
+ * Device pointers only (flags must hold SDNR_DEVICE_PTRS); asynchronous on
+ * the context stream (pair_off[0] and pair_off[nrows] are read back first:
+ * not monotone is SDNR_ERR_INVAL); on a multi-device context it runs on the
+ * primary device; SDNR_TIMING as in sdnr_ecmp_link_loads.  Without an uploaded
+ * graph or without uploaded costs: SDNR_ERR_STATE.  nrows == 0 or no pairs:
+ * SDNR_OK, nothing touched.  One launch.  A row that is not a least-cost
+ * labelling of the graph under the costs in force (a vertex of finite cost > 0
+ * without a next hop, an ordering pass longer than V, a route count above the
+ * double range) is reported by sdnr_synchronize as SDNR_ERR_INVAL; the
+ * offending flow is dropped. */
+int sdnr_cost_ecmp_link_loads(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrows,
+                              const int64_t *pair_off, const int32_t *srcs,
+                              const uint64_t *weight, double *load, uint32_t flags);
+
 /* Flood ports (TopologyManager._is_edge_port / _do_broadcast, reference
  * sdnmpi/topology.py:150-177): is_edge[i] = 1 iff ports[i] is neither end of
  * any link.  Keys are (dense switch id << 32) | port_no; ends (both ends of

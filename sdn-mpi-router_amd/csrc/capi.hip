@@ -61,6 +61,12 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "labelling of the uploaded graph (a vertex without a next hop, a "
                              "level >= V, a route count above the double range) or pair_off is "
                              "not monotone: loads invalid");
+        if (h & kErrCostEcmpLoads)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_ecmp_link_loads: a pcost row is not a "
+                             "least-cost labelling of the uploaded graph under the costs in force "
+                             "(a vertex of finite cost > 0 without a next hop, an ordering pass "
+                             "longer than V, a route count above the double range) or pair_off is "
+                             "not monotone: loads invalid");
         if (h & kErrCostTables)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_tables: V relaxation sweeps did not reach "
                              "the fixed point (link costs outside what sdnr_graph_costs accepts): "
@@ -1257,6 +1263,41 @@ int sdnr_cost_tables(sdnr_ctx *ctx, const int32_t *dst, int32_t ndst, uint32_t *
     }
     SDNR_HIP(hipStreamSynchronize(ctx->stream));
     return sdnr_check_watchdog(ctx);
+}
+
+int sdnr_cost_ecmp_link_loads(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrows,
+                              const int64_t *pair_off, const int32_t *srcs,
+                              const uint64_t *weight, double *load, uint32_t flags)
+{
+    CHECK_CTX(ctx);
+    if (ctx->V < 0)
+        return sdnr_fail(SDNR_ERR_STATE, "sdnr_cost_ecmp_link_loads: no graph uploaded");
+    if (!(flags & SDNR_DEVICE_PTRS))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_ecmp_link_loads: device pointers only");
+    if (nrows < 0) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_ecmp_link_loads: negative count");
+    if (!ctx->has_cost)
+        return sdnr_fail(SDNR_ERR_STATE, "sdnr_cost_ecmp_link_loads: no link costs uploaded for "
+                         "this graph (sdnr_graph_costs)");
+    if (nrows == 0) return SDNR_OK;
+    if (!pcost || !pair_off || !load)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_ecmp_link_loads: null pointer");
+    SDNR_HIP(hipSetDevice(ctx->device));
+    // the bounds of the pair list: pair_off[0], pair_off[nrows] (two int64)
+    int w[4];
+    int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off), 2, w);
+    if (!rc) rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off + nrows), 2, w + 2);
+    if (rc) return rc;
+    const int64_t lo = (int64_t)(((uint64_t)(uint32_t)w[1] << 32) | (uint32_t)w[0]);
+    const int64_t hi = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
+    if (lo < 0 || hi < lo)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_ecmp_link_loads: pair_off not monotone "
+                         "(pair_off[0]=%lld, pair_off[%d]=%lld)", (long long)lo, nrows,
+                         (long long)hi);
+    if (hi == lo || ctx->V == 0) return SDNR_OK;
+    if (!srcs) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_ecmp_link_loads: null pointer");
+    ctx->timed = (flags & SDNR_TIMING) != 0;
+    return sdnr_launch_cost_ecmp_link_loads(ctx, pcost, nrows, pair_off, lo, hi, srcs, weight,
+                                            load, (flags & SDNR_LOADS_SPLIT_HOP) != 0);
 }
 
 int sdnr_apsp(sdnr_ctx *ctx, uint16_t *dist, uint32_t flags)

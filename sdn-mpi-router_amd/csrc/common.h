@@ -189,6 +189,16 @@ constexpr int kErrCostTables = 16384; // sdnr_cost_tables: V sweeps did not reac
 // at most kLoadsScratchBytes in all)
 constexpr int kCostLdsMaxV8 = 5000;
 constexpr int kCostLdsMaxV = 10000;
+constexpr int kErrCostEcmpLoads = 32768; // sdnr_cost_ecmp_link_loads: a pcost row is no least-cost labelling / bad offsets
+
+// sdnr_cost_ecmp_link_loads keeps a row's route counts, flows, costs and
+// depths in LDS (22 bytes per vertex) up to this V -- what the CU's LDS holds,
+// rounded down to a hundred: 7,400, 162,800 of 163,840 bytes --,
+// else the counts, flows and depths in global scratch (20 bytes per vertex and
+// workgroup, at most kLoadsScratchBytes in all)
+constexpr int kCostEcmpBytesPerV = 22;
+constexpr int kCostEcmpLdsMaxV = SDNR_LDS_PER_CU / kCostEcmpBytesPerV / 100 * 100;
+static_assert(kCostEcmpLdsMaxV == 7400 && kCostEcmpLdsMaxV < 0xFFFF, "depths in LDS are u16");
 
 // error plumbing (capi.hip)
 int sdnr_fail(int code, const char *fmt, ...);
@@ -265,5 +275,10 @@ int sdnr_launch_ecmp_link_loads(sdnr_ctx *ctx, const uint16_t *d_dist, int32_t n
 // least-cost tables under the uploaded per-link costs (cost_tables.hip)
 int sdnr_launch_cost_tables(sdnr_ctx *ctx, const int32_t *d_dst, int32_t ndst, uint32_t *d_pcost,
                             int32_t *d_nh, int32_t *d_nh_port);
+// per-link loads of a demand split over every least-cost route (cost_ecmp_loads.hip)
+int sdnr_launch_cost_ecmp_link_loads(sdnr_ctx *ctx, const uint32_t *d_pcost, int32_t nrows,
+                                     const int64_t *d_pair_off, int64_t pair_lo, int64_t pair_hi,
+                                     const int32_t *d_srcs, const uint64_t *d_weight,
+                                     double *d_load, bool hop);
 int sdnr_launch_edge_ports(sdnr_ctx *ctx, const uint64_t *d_ends, int32_t nends,
                            const uint64_t *d_ports, int32_t nports, uint8_t *d_is_edge);

@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_last_kernel_ms", "sdnr_last_kernel", "sdnr_last_launches", "sdnr_last_sweeps",
     "sdnr_edge_ports", "sdnr_dfs_rows_affected", "sdnr_link_loads",
     "sdnr_ecmp_link_loads", "sdnr_graph_costs", "sdnr_cost_tables",
+    "sdnr_cost_ecmp_link_loads",
 )
 
 
@@ -106,6 +107,7 @@ def _bind(L):
         "sdnr_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, vp, u32], c_int),
         "sdnr_graph_costs": ([vp, vp], c_int),
         "sdnr_cost_tables": ([vp, vp, i32, vp, vp, vp, u32], c_int),
+        "sdnr_cost_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, vp, u32], c_int),
     }
     # an A/B build named by SDNROUTE_LIB may predate some entry points: those
     # stay unbound (calling one raises AttributeError); the in-tree library
@@ -472,6 +474,22 @@ class Context(object):
         flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_SPLIT_HOP if hop else 0)
         _check(self._lib.sdnr_ecmp_link_loads(
             self._h, ctypes.c_void_p(dist_ptr) if dist_ptr else None, int(nrows),
+            ctypes.c_void_p(pair_off_ptr) if pair_off_ptr else None,
+            ctypes.c_void_p(srcs_ptr) if srcs_ptr else None,
+            ctypes.c_void_p(weight_ptr) if weight_ptr else None,
+            ctypes.c_void_p(load_ptr) if load_ptr else None, flags))
+
+    def cost_ecmp_link_loads_device(self, pcost_ptr, nrows, pair_off_ptr, srcs_ptr, weight_ptr,
+                                    load_ptr, hop=False, timing=False):
+        """Add the per-link loads of a demand split over every least-cost
+        route of [nrows][V] u32 pcost rows (sdnr_cost_tables', under the costs
+        in force) into ``load`` (f64 [E], CSR edge order; the caller zeroes
+        it): sdnr_cost_ecmp_link_loads, device pointers, asynchronous.
+        ``weight_ptr`` 0: every pair weighs 1; ``hop``: split evenly per
+        switch (SDNR_LOADS_SPLIT_HOP) instead of per route."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_SPLIT_HOP if hop else 0)
+        _check(self._lib.sdnr_cost_ecmp_link_loads(
+            self._h, ctypes.c_void_p(pcost_ptr) if pcost_ptr else None, int(nrows),
             ctypes.c_void_p(pair_off_ptr) if pair_off_ptr else None,
             ctypes.c_void_p(srcs_ptr) if srcs_ptr else None,
             ctypes.c_void_p(weight_ptr) if weight_ptr else None,

@@ -42,7 +42,9 @@ from .graph import empty_csr
 __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "shortest_paths_lex", "count_shortest_paths", "ECMP_LIMIT", "DEFAULT_TABLE_BUDGET", "tree_layout", "dfs_row_bytes",
            "sp_row_bytes", "link_loads_host", "ecmp_link_loads_host", "cost_tables_host",
-           "check_link_costs", "COST_INF", "COST_MAX", "COST_LDS_MAX_V", "COST_LDS_B8_MAX_V"]
+           "check_link_costs", "COST_INF", "COST_MAX", "COST_LDS_MAX_V", "COST_LDS_B8_MAX_V",
+           "cost_ecmp_link_loads_host", "least_cost_paths_lex", "count_least_cost_paths",
+           "COST_ECMP_LDS_MAX_V"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -477,6 +479,86 @@ def cost_tables_host(csr, cost, dsts):
     return pcost, nh, nhp
 
 
+COST_ECMP_LDS_MAX_V = 7400      # csrc/common.h kCostEcmpLdsMaxV: ECMP-under-costs row state in LDS
+
+
+def _pcost_u32(pcost):
+    """pcost rows as numpy uint32 (the engine keeps u32 costs in int32 planes)."""
+    p = np.asarray(pcost)
+    if p.dtype == np.int32:
+        return p.view(np.uint32)
+    if p.dtype != np.uint32:
+        p = (p.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
+    return p
+
+
+def cost_ecmp_link_loads_host(csr, cost, pcost, rows, srcs, weights=None, split="route"):
+    """numpy float64 restatement of sdnr_cost_ecmp_link_loads (the CPU tests'
+    engine double and an independent check of cost_ecmp_loads.hip): float64
+    [E] loads of pairs (row ``rows[i]`` of ``pcost``, source switch
+    ``srcs[i]``, weight ``weights[i]`` or 1) split over every least-cost route
+    under the link costs ``cost`` (uint32 [E], CSR edge order).
+
+    ``pcost``: [k, V] least path costs toward each row's destination, uint32
+    or the engine's int32-holding-u32 plane (COST_INF / -1: no route).
+    Deliberately not the kernel's order (longest next-hop chains): the
+    next-hop links (pcost[n] + cost == pcost[x]) of a used row are sorted by
+    the pcost of their tail once; a next hop has a strictly smaller pcost, so
+    sigma (least-cost route counts; ``split="hop"``: next-hop counts) is
+    summed over the groups of equal pcost ascending and the flow is pushed
+    over them descending.  A row that is not a least-cost labelling (a vertex
+    of finite cost > 0 without a live next hop, a count beyond the double
+    range) raises ValueError."""
+    if split not in SPLITS:
+        raise ValueError("split must be 'route' or 'hop'")
+    V, E = int(csr.V), int(csr.E)
+    load = np.zeros(E, np.float64)
+    rows = np.asarray(rows, np.int64)
+    srcs = np.asarray(srcs, np.int64)
+    c64 = check_link_costs(csr, cost).astype(np.int64)
+    if rows.size == 0 or E == 0:
+        return load
+    w = np.ones(rows.shape[0], np.float64) if weights is None else \
+        np.asarray(weights, np.uint64).astype(np.float64)
+    pcost = _pcost_u32(pcost)
+    rp = np.asarray(csr.row_ptr, np.int64)
+    esrc = np.repeat(np.arange(V, dtype=np.int64), np.diff(rp))
+    edst = np.asarray(csr.col, np.int64)
+    ok = np.nonzero((srcs >= 0) & (srcs < V) & (w > 0))[0]
+    ok = ok[np.argsort(rows[ok], kind="stable")]           # the pairs grouped by row
+    used, first = np.unique(rows[ok], return_index=True)
+    bounds = np.append(first, ok.shape[0])
+    for k, r in enumerate(used.tolist()):
+        pc = pcost[r].astype(np.int64)
+        fin = pc != COST_INF
+        mine = ok[bounds[k]:bounds[k + 1]]
+        s = srcs[mine]
+        keep = fin[s] & (pc[s] > 0)                        # not unreached, not s == d
+        flow = np.bincount(s[keep], w[mine][keep], minlength=V).astype(np.float64)
+        dag = np.nonzero(fin[esrc] & (pc[esrc] > 0) & fin[edst] & (pc[edst] + c64 == pc[esrc]))[0]
+        dag = dag[np.argsort(pc[esrc[dag]], kind="stable")]
+        _, start = np.unique(pc[esrc[dag]], return_index=True)
+        end = np.append(start[1:], dag.shape[0])
+        sigma = np.zeros(V, np.float64)
+        if split == "hop":
+            sigma += np.bincount(esrc[dag], minlength=V)
+        else:
+            sigma[pc == 0] = 1.0
+            for a, b in zip(start.tolist(), end.tolist()):
+                e = dag[a:b]
+                sigma += np.bincount(esrc[e], sigma[edst[e]], minlength=V)
+        if (fin & (pc > 0) & ~(sigma > 0)).any() or not np.isfinite(sigma).all():
+            raise ValueError("cost_ecmp_link_loads_host: a row is not a least-cost labelling "
+                             "of the graph under these costs")
+        for a, b in zip(start.tolist()[::-1], end.tolist()[::-1]):
+            e = dag[a:b]
+            x, n = esrc[e], edst[e]
+            g = flow[x] / sigma[x] if split == "hop" else flow[x] * (sigma[n] / sigma[x])
+            load[e] += g                                   # (a link appears in one group)
+            flow += np.bincount(n, g, minlength=V)
+    return load
+
+
 class RouteEngine(object):
     """The GPU route engine of one TopologyDB: HIP device ``device`` (int),
     or the devices of a list (single-process multi-GPU, sources sharded over
@@ -842,6 +924,55 @@ class RouteEngine(object):
                                         d_w.data_ptr() if d_w is not None else 0,
                                         load.data_ptr(), hop=split == "hop", timing=timing)
         self.ctx.synchronize()              # raises if a row was no BFS labelling
+        return load.cpu().numpy()
+
+    def cost_ecmp_link_loads(self, export, cost, pcost, rows, srcs, weights=None, split="route",
+                             timing=False):
+        """Per-link loads of a demand split over every least-cost route under
+        the per-link costs ``cost`` (cost_ecmp_loads.hip,
+        sdnr_cost_ecmp_link_loads): numpy float64 [E] in the CSR's edge order.
+
+        ``cost``: uint32 [E], uploaded as ``cost_tables`` uploads it;
+        ``pcost``: [k, V] least-cost rows computed under those costs, a device
+        tensor (int32 holding u32, as ``cost_tables`` returns it) or a numpy
+        array; rows without pairs are skipped.  Pair i enters at dense switch
+        ``srcs[i]`` of row ``rows[i]`` and weighs ``weights[i]`` (u64, None:
+        1).  ``split`` as in ``ecmp_link_loads``.  Sums are f64 atomics: equal
+        to the host restatement within rounding, not bit-reproducible."""
+        if split not in SPLITS:
+            raise ValueError("split must be 'route' or 'hop'")
+        self.set_link_costs(export, cost)
+        t = self._torch
+        E = int(export.csr.E)
+        rows = np.asarray(rows, np.int64)
+        if isinstance(pcost, np.ndarray):
+            pcost = t.from_numpy(np.ascontiguousarray(_pcost_u32(pcost)).view(np.int32)).to(
+                self.dev)
+        nrows = int(pcost.shape[0])
+        if rows.size == 0 or nrows == 0 or E == 0:
+            return np.zeros(E, np.float64)
+        if rows.min() < 0 or rows.max() >= nrows:
+            raise ValueError("cost_ecmp_link_loads: a pair names a row outside the table")
+        if pcost.element_size() != 4:
+            raise ValueError("cost_ecmp_link_loads: pcost rows are 32-bit")
+        order, off = _pairs_by_row(rows, nrows)
+        V = int(export.csr.V)
+        s = np.asarray(srcs, np.int64)[order]
+        s = np.where((s < 0) | (s >= V), -1, s).astype(np.int32)
+        pcost = pcost.contiguous()
+        d_off = t.from_numpy(off).to(self.dev)
+        d_src = t.from_numpy(s).to(self.dev)
+        d_w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights, np.uint64)[order])
+            d_w = t.from_numpy(w.view(np.int64)).to(self.dev)
+        load = t.zeros(E, dtype=t.float64, device=self.dev)
+        self._ready()
+        self.ctx.cost_ecmp_link_loads_device(pcost.data_ptr(), nrows, d_off.data_ptr(),
+                                             d_src.data_ptr(),
+                                             d_w.data_ptr() if d_w is not None else 0,
+                                             load.data_ptr(), hop=split == "hop", timing=timing)
+        self.ctx.synchronize()              # raises if a row was no least-cost labelling
         return load.cpu().numpy()
 
     def edge_ports(self, ends, ports):
@@ -1333,6 +1464,71 @@ def shortest_paths_lex(row_ptr, col, dist_row, s, d):
                 acc.pop()
 
     walk(int(s))
+    return out
+
+
+def _least_cost_next_hops(row_ptr, col, cost, pc, x):
+    """Out-neighbours n of x, ascending, with pc[n] finite and cost(x -> n) +
+    pc[n] == pc[x] (pc: Python ints, COST_INF where there is no route)."""
+    want = pc[x]
+    return [int(col[e]) for e in range(int(row_ptr[x]), int(row_ptr[x + 1]))
+            if pc[int(col[e])] != COST_INF and pc[int(col[e])] + int(cost[e]) == want]
+
+
+def count_least_cost_paths(row_ptr, col, cost, pcost_row, s, d, limit=None):
+    """Number of least-cost s->d routes under the link costs: a DP over the
+    part of the least-cost DAG reachable from s, in ascending pcost order (the
+    weighted twin of count_shortest_paths).  Stops counting once ``limit`` is
+    passed and returns limit + 1."""
+    pc = _pcost_u32(pcost_row).astype(np.int64).tolist()
+    s, d = int(s), int(d)
+    if pc[s] == COST_INF:
+        return 0
+    nxt = {}
+    todo = [s]
+    while todo:                       # the DAG below s
+        x = todo.pop()
+        if x in nxt:
+            continue
+        nxt[x] = [] if x == d else _least_cost_next_hops(row_ptr, col, cost, pc, x)
+        todo.extend(n for n in nxt[x] if n not in nxt)
+    cap = None if limit is None else int(limit) + 1
+    cnt = {}
+    for x in sorted(nxt, key=lambda v: pc[v]):            # a next hop costs strictly less
+        c = 1 if x == d else sum(cnt[n] for n in nxt[x])
+        cnt[x] = c if cap is None else min(c, cap)
+    return cnt.get(s, 0)
+
+
+def least_cost_paths_lex(row_ptr, col, cost, pcost_row, s, d):
+    """Every least-cost s->d vertex sequence under the link costs ``cost``
+    (uint32 [E]) in lexicographic vertex order -- the weighted counterpart of
+    shortest_paths_lex: walk the least-cost DAG (pcost_row = least path costs
+    to d) taking successors ascending.  [] without a route; sets above
+    ECMP_LIMIT routes raise MemoryError before any is built."""
+    pc = _pcost_u32(pcost_row).astype(np.int64).tolist()
+    s, d = int(s), int(d)
+    if pc[s] == COST_INF:
+        return []
+    if count_least_cost_paths(row_ptr, col, cost, pcost_row, s, d, ECMP_LIMIT) > ECMP_LIMIT:
+        raise MemoryError("ECMP set too large to enumerate")
+    if s == d:
+        return [[s]]
+    out = []
+    # (iterative: a least-cost route may be thousands of links long)
+    acc, stack = [s], [iter(_least_cost_next_hops(row_ptr, col, cost, pc, s))]
+    while stack:
+        n = next(stack[-1], None)
+        if n is None:
+            stack.pop()
+            acc.pop()
+            continue
+        acc.append(n)
+        if n == d:
+            out.append(list(acc))
+            acc.pop()
+            continue
+        stack.append(iter(_least_cost_next_hops(row_ptr, col, cost, pc, n)))
     return out
 
 

@@ -27,7 +27,8 @@ first route query raises (``sdnmpi_amd._native.NativeUnavailable`` /
 import numpy as np
 
 from ..engine import (COST_MAX, DEFAULT_TABLE_BUDGET, INT32, RouteEngine, TableCache, _gather,
-                      _host, _take, _torch, _u16, check_link_costs, shortest_paths_lex, tree_path)
+                      _host, _take, _torch, _u16, check_link_costs, least_cost_paths_lex,
+                      shortest_paths_lex, tree_path)
 from ..graph import TrackedDict, Versions, export_graph, update_export
 from ..incremental import edge_diff
 
@@ -982,17 +983,21 @@ class TopologyDB(object):
         out.append(last)
         return out
 
-    def find_route_least_cost(self, src_mac, dst_mac):
+    def find_route_least_cost(self, src_mac, dst_mac, multiple=False):
         """The least-cost route between two hosts (or switch-local ports)
         under the link costs, in ``find_route``'s format and with its endpoint
         rules: [] for an unknown MAC or an unreachable destination, the one
         last-hop entry for two endpoints on one switch.  Among equal-cost
         routes the lexicographically smallest dpid sequence, the tie rule of
         ``find_route(multiple=True)[0]`` -- which it equals while every cost
-        is 1."""
-        return self.find_routes_least_cost([(src_mac, dst_mac)])[0]
+        is 1.  With ``multiple=True`` the list of EVERY least-cost route, in
+        ``find_route(multiple=True)``'s format and order (lexicographic dpid
+        sequences; [] where the single form returns []): the ECMP set an OSPF
+        fabric balances over, and ``find_route(multiple=True)`` itself while
+        every cost is 1."""
+        return self.find_routes_least_cost([(src_mac, dst_mac)], multiple)[0]
 
-    def find_routes_least_cost(self, pairs):
+    def find_routes_least_cost(self, pairs, multiple=False):
         """:meth:`find_route_least_cost` over many (src_mac, dst_mac) pairs;
         the destination rows are computed once for all of them."""
         pairs = list(pairs)
@@ -1006,6 +1011,7 @@ class TopologyDB(object):
             ends[i] = (ex.index[ea[0]], ex.index[eb[0]], self._last_hop(eb[0], eb[1], b))
         want = sorted(set(e[1] for e in ends.values()))
         step = self._cost_cap(ex)
+        cost = self._cost_vector(ex) if multiple and want else None
         for c0 in range(0, len(want), step):        # a budget's worth of rows at a time
             chunk = want[c0:c0 + step]
             m = self._cost_rows(ex, chunk)
@@ -1013,7 +1019,11 @@ class TopologyDB(object):
             host = [_host(_take(t, idx)) for t in m["tabs"]]
             at = {d: k for k, d in enumerate(chunk)}
             for i, (s, d, last) in ends.items():
-                if d in at:
+                if d in at and multiple:
+                    seqs = least_cost_paths_lex(ex.csr.row_ptr, ex.csr.col, cost,
+                                                host[0][at[d]], s, d)
+                    out[i] = [self._seq_fdb(ex, q, last) for q in seqs]
+                elif d in at:
                     k = at[d]
                     out[i] = self._least_cost_fdb(ex, s, d, last,
                                                   (host[0][k].view(np.int32), host[1][k],
@@ -1067,6 +1077,76 @@ class TopologyDB(object):
         :meth:`mpi_link_loads`)."""
         pairs, weights = self._rank_pairs(rank_to_mac, traffic)
         return self.least_cost_link_loads(pairs, weights)
+
+    # -- ECMP over the least-cost routes ----------------------------------
+    def _switch_pair_cost_ecmp_loads(self, ex, sv, dv, w, split):
+        """(load float64 [E], reach bool [n]) of switch pairs (dense ids sv ->
+        dv, weights w u64) split over every least-cost route: one
+        sdnr_cost_ecmp_link_loads call per budget-sized chunk of destination
+        rows, over the memoised pcost plane as it is (rows without pairs are
+        skipped by the kernel)."""
+        if split not in ("route", "hop"):
+            raise ValueError("split must be 'route' or 'hop'")
+        E = int(ex.csr.E)
+        load = np.zeros(E, np.float64)
+        reach = np.zeros(sv.shape[0], bool)
+        if sv.size == 0:
+            return load, reach
+        want = sorted(set(dv.tolist()))
+        step = self._cost_cap(ex)
+        cost = self._cost_vector(ex)
+        for c0 in range(0, len(want), step):
+            chunk = want[c0:c0 + step]
+            m = self._cost_rows(ex, chunk)
+            mine = np.nonzero(np.isin(dv, np.asarray(chunk, np.int64)))[0]
+            slots = np.asarray([m["slot"][v] for v in dv[mine].tolist()], np.int64)
+            pc = m["tabs"][0]
+            # pcost is held as int32: COST_INF reads -1
+            reach[mine] = _gather(pc, slots, sv[mine]) != -1
+            load += self.engine.cost_ecmp_link_loads(ex, cost, pc, slots, sv[mine], w[mine],
+                                                     split)
+        return load, reach
+
+    def least_cost_ecmp_link_loads(self, pairs, weights=None, split="route"):
+        """:meth:`ecmp_link_loads` under the link costs: every (src_mac,
+        dst_mac) pair spreads ``weights[i]`` over ALL its least-cost routes --
+        what the links carry once a link is costed up and the traffic spreads
+        over the surviving equal-cost routes -- as a :class:`SplitLinkLoads`.
+
+        Defining property: ``least_cost_ecmp_link_loads(pairs, w).as_dict()
+        [(dpid, port)]`` is the sum over i of ``w[i] / N_i`` times the number
+        of routes in ``find_route_least_cost(*pairs[i], multiple=True)`` that
+        hold that entry, where N_i is the number of those routes.
+        ``split="hop"`` divides the traffic at every switch evenly over its
+        least-cost next hops instead.  Unknown hosts and unreachable pairs
+        contribute nothing; repeated pairs add.  No route is enumerated
+        (cost_ecmp_loads.hip pushes the demand down the least-cost DAG of each
+        destination); link loads are float64 sums, equal to the definition
+        within rounding (not bit-reproducible between runs), the last hops
+        exact uint64.  With no cost set it is :meth:`ecmp_link_loads`."""
+        return self._pair_loads(
+            pairs, weights,
+            lambda ex, sv, dv, w: self._switch_pair_cost_ecmp_loads(ex, sv, dv, w, split),
+            SplitLinkLoads)
+
+    def all_pairs_least_cost_ecmp_link_loads(self, split="route"):
+        """:meth:`least_cost_ecmp_link_loads` over every ordered pair of
+        distinct hosts with weight 1, from the per-switch host counts (as
+        :meth:`all_pairs_link_loads`)."""
+        got = self._all_pairs_loads(
+            lambda ex, sv, dv, w: self._switch_pair_cost_ecmp_loads(ex, sv, dv, w, split),
+            SplitLinkLoads)
+        if got is None:
+            macs = list(self.hosts)
+            return self.least_cost_ecmp_link_loads(
+                [(a, b) for a in macs for b in macs if a != b], None, split)
+        return got
+
+    def mpi_least_cost_ecmp_link_loads(self, rank_to_mac, traffic=None, split="route"):
+        """:meth:`least_cost_ecmp_link_loads` of an MPI job (``traffic`` as in
+        :meth:`mpi_link_loads`)."""
+        pairs, weights = self._rank_pairs(rank_to_mac, traffic)
+        return self.least_cost_ecmp_link_loads(pairs, weights, split)
 
     def find_routes(self, pairs, multiple=False):
         """find_route over many (src_mac, dst_mac) pairs; tables are computed
