@@ -120,6 +120,13 @@ int sdnr_graph_upload(sdnr_ctx *ctx, int32_t V, int32_t E,
 int sdnr_graph_info(const sdnr_ctx *ctx, int32_t *V, int32_t *E,
                     int32_t *max_degree);
 
+/* Twin classes of the uploaded graph: rep[v] (V entries, host buffer) = the
+ * smallest vertex with the same out-row and the same in-row as v (v itself
+ * when there is none, or when v's row holds a self-loop).  The default-route
+ * rows of a class differ in a few entries only, so a large sdnr_dfs_tables*
+ * batch searches one member per class and derives the other rows. */
+int sdnr_graph_twin_reps(sdnr_ctx *ctx, int32_t *rep);
+
 /* Default route, find_route(src, dst) (multiple=False) -> _find_route_dfs
  * (topology_db.py:59-84, called from :181-188), batched over all
  * destinations: for every source src[i] the tree of first pushes of one full
@@ -449,6 +456,11 @@ int sdnr_last_kernel_ms(sdnr_ctx *ctx, float *ms);
  * min-plus squaring passes of sdnr_apsp, the BFS levels of the level-by-level
  * shortest kernel, 1 for single-launch kernels (0 before the first call). */
 int sdnr_last_launches(const sdnr_ctx *ctx, int32_t *launches);
+
+/* Sources the last sdnr_dfs_tables* call searched (waits for that call): the
+ * batch size, or, when the call folded twin classes, one per class present
+ * in the batch -- the other rows were derived (0 before the first call). */
+int sdnr_last_dfs_searched(sdnr_ctx *ctx, int32_t *n);
 
 /* Bellman-Ford sweeps of the last sdnr_apsp call (the most any 8-row block
  * ran, summed over its relaxation launches; 0 with SDNROUTE_APSP_RELAX=0). */

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <array>
 #include <map>
 #include <string>
@@ -139,6 +140,9 @@ static void free_graph(sdnr_ctx *c)
     if (c->cost) (void)hipFree(c->cost);         // the costs follow the edge order
     c->cost = nullptr;
     c->has_cost = false;
+    if (c->twin_rep) (void)hipFree(c->twin_rep);
+    c->twin_rep = nullptr;
+    c->has_twins = false;
     if (c->radj16 && c->radj_owned) (void)hipFree(c->radj16);
     if (c->runs) (void)hipFree(c->runs);
     c->runs = nullptr;
@@ -354,6 +358,7 @@ int sdnr_destroy(sdnr_ctx *ctx)
     free_graph(ctx);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->scratch2) (void)hipFree(ctx->scratch2);
+    if (ctx->scratch3) (void)hipFree(ctx->scratch3);
     if (ctx->wq) (void)hipFree(ctx->wq);
     if (ctx->dmat) (void)hipFree(ctx->dmat);
     if (ctx->anc) (void)hipFree(ctx->anc);
@@ -475,6 +480,72 @@ static int upload_dict(sdnr_ctx *ctx, int32_t V, int32_t W, const int32_t *row_p
     return SDNR_OK;
 }
 
+// Twin classes for the DFS fold (dfs.hip): twin_rep[v] = the
+// smallest vertex with v's out-row and v's in-row.  A vertex with a self-loop
+// stays alone: with equal rows, "u is in v's row" means u is in its own, so
+// leaving those out is the whole of "neither is in the other's row".  Rows
+// are hashed, vertices sorted by hash, and equal hashes compared exactly.
+static int upload_twins(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *row_ptr,
+                        const int32_t *col)
+{
+    if (V == 0) return SDNR_OK;
+    std::vector<int32_t> in_ptr((size_t)V + 1, 0), in_col((size_t)E);
+    for (int32_t e = 0; e < E; ++e) in_ptr[(size_t)col[e] + 1]++;
+    for (int32_t v = 0; v < V; ++v) in_ptr[(size_t)v + 1] += in_ptr[v];
+    {
+        std::vector<int32_t> fill(in_ptr.begin(), in_ptr.end() - 1);
+        for (int32_t u = 0; u < V; ++u)           // ascending u: in-rows come out sorted
+            for (int32_t e = row_ptr[u]; e < row_ptr[u + 1]; ++e) in_col[fill[col[e]]++] = u;
+    }
+    std::vector<uint64_t> hash((size_t)V);
+    std::vector<int32_t> rep((size_t)V), order;
+    auto mix = [](uint64_t h, uint64_t x) {
+        h ^= x + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
+        return h * 0xFF51AFD7ED558CCDull;
+    };
+    for (int32_t v = 0; v < V; ++v) {
+        rep[v] = v;
+        bool loop = false;
+        uint64_t h = (uint64_t)(row_ptr[v + 1] - row_ptr[v]);
+        for (int32_t e = row_ptr[v]; e < row_ptr[v + 1]; ++e) {
+            loop |= col[e] == v;
+            h = mix(h, (uint64_t)col[e]);
+        }
+        h = mix(h, ~(uint64_t)(in_ptr[v + 1] - in_ptr[v]));
+        for (int32_t e = in_ptr[v]; e < in_ptr[v + 1]; ++e) h = mix(h, (uint64_t)in_col[e]);
+        hash[v] = h;
+        if (!loop) order.push_back(v);
+    }
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+        return hash[a] != hash[b] ? hash[a] < hash[b] : a < b;
+    });
+    auto same = [](const int32_t *ptr, const int32_t *ids, int32_t a, int32_t b) {
+        const int32_t n = ptr[a + 1] - ptr[a];
+        return n == ptr[b + 1] - ptr[b] &&
+               (n == 0 || !memcmp(ids + ptr[a], ids + ptr[b], sizeof(int32_t) * (size_t)n));
+    };
+    bool any = false;
+    for (size_t i = 0, j; i < order.size(); i = j) {
+        for (j = i + 1; j < order.size() && hash[order[j]] == hash[order[i]]; ++j) {
+            const int32_t v = order[j];
+            for (size_t k = i; k < j; ++k) {      // class heads of this hash, ascending
+                const int32_t r = order[k];
+                if (rep[r] == r && same(row_ptr, col, r, v) &&
+                    same(in_ptr.data(), in_col.data(), r, v)) {
+                    rep[v] = r;
+                    any = true;
+                    break;
+                }
+            }
+        }
+    }
+    int rc = upload(&ctx->twin_rep, rep.data(), sizeof(int32_t) * (size_t)V, 0, ctx->stream);
+    if (rc) return rc;
+    SDNR_HIP(hipStreamSynchronize(ctx->stream));  // before rep goes away
+    ctx->has_twins = any;
+    return SDNR_OK;
+}
+
 int sdnr_graph_upload(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *row_ptr,
                       const int32_t *col, const int32_t *port)
 {
@@ -522,6 +593,10 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
     if ((rc = upload(&ctx->row_ptr, row_ptr, sizeof(int32_t) * ((size_t)V + 1), 0, ctx->stream)) ||
         (rc = upload(&ctx->col, col, sizeof(int32_t) * (size_t)E, kPad, ctx->stream)) ||
         (rc = upload(&ctx->port, port, sizeof(int32_t) * (size_t)E, kPad, ctx->stream))) {
+        free_graph(ctx);
+        return rc;
+    }
+    if ((rc = upload_twins(ctx, V, E, row_ptr, col))) {
         free_graph(ctx);
         return rc;
     }
@@ -804,6 +879,12 @@ static int begin_call(sdnr_ctx *ctx, int32_t n, const void *ids, uint32_t flags,
     SDNR_HIP(hipSetDevice(ctx->device));
     ctx->timed = (flags & SDNR_TIMING) != 0;
     ctx->last_launches = 1;
+    ctx->dfs_nsrc = 0;                           // sdnr_last_dfs_searched: the shards of this call
+    ctx->dfs_folded = false;
+    for (int k = 0; k < ctx->npeers; ++k) {
+        ctx->peers[k]->dfs_nsrc = 0;
+        ctx->peers[k]->dfs_folded = false;
+    }
     return SDNR_OK;
 }
 
@@ -1518,6 +1599,38 @@ int sdnr_last_sweeps(const sdnr_ctx *ctx, int32_t *sweeps)
     CHECK_CTX(ctx);
     if (!sweeps) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_last_sweeps: null out");
     *sweeps = ctx->last_sweeps;
+    return SDNR_OK;
+}
+
+int sdnr_graph_twin_reps(sdnr_ctx *ctx, int32_t *rep)
+{
+    CHECK_CTX(ctx);
+    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_graph_twin_reps: no graph uploaded");
+    if (!rep && ctx->V > 0) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_graph_twin_reps: null out");
+    if (ctx->V == 0) return SDNR_OK;
+    SDNR_HIP(hipSetDevice(ctx->device));
+    SDNR_HIP(hipMemcpy(rep, ctx->twin_rep, sizeof(int32_t) * (size_t)ctx->V,
+                       hipMemcpyDeviceToHost));
+    return SDNR_OK;
+}
+
+int sdnr_last_dfs_searched(sdnr_ctx *ctx, int32_t *n)
+{
+    CHECK_CTX(ctx);
+    if (!n) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_last_dfs_searched: null out");
+    int32_t sum = 0;
+    for (int k = 0; k <= ctx->npeers; ++k) {     // every shard of the last call
+        sdnr_ctx *c = k == 0 ? ctx : ctx->peers[k - 1];
+        int32_t got = c->dfs_nsrc;
+        if (c->dfs_folded) {                     // the prep kernel's count (head of scratch3)
+            SDNR_HIP(hipSetDevice(c->device));
+            SDNR_HIP(hipStreamSynchronize(c->stream));
+            SDNR_HIP(hipMemcpy(&got, c->scratch3, sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+        sum += got;
+    }
+    SDNR_HIP(hipSetDevice(ctx->device));
+    *n = sum;
     return SDNR_OK;
 }
 

@@ -88,6 +88,16 @@ struct sdnr_ctx {
     uint64_t *adjb = nullptr;
     uint8_t *adjp = nullptr;
     uint32_t *radjx = nullptr;
+    // twin classes: twin_rep[v] = smallest vertex with v's
+    // out-row and in-row (v itself when its row holds a self-loop); the DFS
+    // rows of a class differ in 2 + |row| entries, so a batch searches one
+    // member per class and derives the others (sdnr_launch_dfs)
+    int32_t *twin_rep = nullptr;
+    bool has_twins = false;             // some class has more than one member
+    // the last DFS launch on this context: its batch size, and whether it
+    // folded (then the searched count is the int at the head of scratch3)
+    int32_t dfs_nsrc = 0;
+    bool dfs_folded = false;
 
     // grow-only device scratch / staging
     void *scratch = nullptr;
@@ -96,6 +106,8 @@ struct sdnr_ctx {
     size_t stage_bytes = 0;
     void *scratch2 = nullptr;           // int32 tables behind a packed-table call
     size_t scratch2_bytes = 0;
+    void *scratch3 = nullptr;           // the twin fold's lists and leader tables (dfs.hip)
+    size_t scratch3_bytes = 0;
     void *wq = nullptr;                 // source work queue of the split DFS (kFlagCuMap)
     size_t wq_bytes = 0;
     void *dmat = nullptr;               // V x V distances behind APSP-derived shortest tables

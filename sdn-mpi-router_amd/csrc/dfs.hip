@@ -2731,9 +2731,10 @@ __global__ __launch_bounds__(256) void dfs_hops16_kernel(size_t n, const int32_t
         out[i] = (uint16_t)h[i];
 }
 
-int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
-                    int32_t *d_parent, int32_t *d_port, int32_t *d_hops, uint32_t *d_tree,
-                    bool slots, bool hops16)
+// the strategy dispatch: one search per entry of d_src
+static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
+                        int32_t *d_parent, int32_t *d_port, int32_t *d_hops, uint32_t *d_tree,
+                        bool slots = false, bool hops16 = false)
 {
     const int V = ctx->V;
     if (nsrc == 0 || V == 0) return SDNR_OK;
@@ -2817,14 +2818,14 @@ int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
         int32_t *tp = static_cast<int32_t *>(ctx->scratch2);
         int32_t *th = h16 ? tp + 2 * n : d_hops;
         if (!packed) {                           // int32 tables, u16 hop counts
-            if ((rc = sdnr_launch_dfs(ctx, d_src, nsrc, d_parent, d_port, tp, nullptr))) return rc;
+            if ((rc = dfs_dispatch(ctx, d_src, nsrc, d_parent, d_port, tp, nullptr))) return rc;
             hipLaunchKernelGGL(dfs_hops16_kernel, dim3(ctx->num_cus * 8), dim3(256), 0,
                                ctx->stream, n, tp, reinterpret_cast<uint16_t *>(d_hops));
             SDNR_HIP(hipGetLastError());
             if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev1, ctx->stream));
             return SDNR_OK;
         }
-        if ((rc = sdnr_launch_dfs(ctx, d_src, nsrc, tp, tp + n, th, nullptr))) return rc;
+        if ((rc = dfs_dispatch(ctx, d_src, nsrc, tp, tp + n, th, nullptr))) return rc;
         if (h16)
             hipLaunchKernelGGL(dfs_hops16_kernel, dim3(ctx->num_cus * 8), dim3(256), 0,
                                ctx->stream, n, th, reinterpret_cast<uint16_t *>(d_hops));
@@ -3034,5 +3035,306 @@ int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
     }
     SDNR_HIP(hipGetLastError());
     if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    return SDNR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Twin fold.  Two switches with the same out-row and the
+// same in-row, neither in the other's row (ctx->twin_rep, capi.hip), have the
+// same DFS row up to 2 + |row| entries: the searches run step for step alike
+// with the two in exchanged roles, the other twin only ever an inert stack
+// entry (all its out-neighbours are marked by the root's pop).  A batch
+// searches the first member of every class it holds (the leader) into a
+// scratch table set and derives every caller row from its leader's:
+//   prep    leaders, compacted to the front of a source list padded with -1
+//           (empty rows), and every position's leader row and leader
+//   search  the unchanged dispatch over that list
+//   derive  row copy + the 2 + |row| patched entries, in the layout's encoding
+// ---------------------------------------------------------------------------
+constexpr int kFoldPrepThreads = 1024;
+constexpr int kFoldDeriveThreads = 256;
+constexpr int kFoldLdsMaxV = 8000;                       // two int tables of V entries in 64 KB
+constexpr size_t kFoldScratchBytes = (size_t)1 << 30;    // above this the batch is not folded
+
+// one workgroup.  Two tables indexed by class (twin_rep): first = the lowest
+// batch position of the class in this batch, slot = its row in the compacted
+// list; in LDS (lds != 0: V <= kFoldLdsMaxV, the whole table initialised
+// while the sources load) or in global memory (only the entries this batch
+// touches are initialised).  The leaders keep their batch order in csrc[0 ..
+// count), the rest of csrc is -1; lead[i] = leader row of position i (-1:
+// src[i] is no vertex), lsrc[i] = that leader's source
+__global__ __launch_bounds__(kFoldPrepThreads) void dfs_fold_prep_kernel(
+    int V, int nsrc, int lds, const int32_t *__restrict__ src, const int32_t *__restrict__ rep,
+    int32_t *gtab, int32_t *__restrict__ csrc, int32_t *__restrict__ lead,
+    int32_t *__restrict__ lsrc, int32_t *__restrict__ count)
+{
+    constexpr int NWV = kFoldPrepThreads / SDNR_WAVE;
+    constexpr int kNone = 0x7FFFFFFF;
+    extern __shared__ __attribute__((aligned(16))) int32_t fold_tab[];
+    __shared__ int wsum[NWV];
+    int32_t *first = lds ? fold_tab : gtab;
+    int32_t *slot = first + V;
+    const int tid = (int)threadIdx.x, lane = lane_id(), w = tid >> 6;
+    if (lds) {
+        for (int v = tid; v < V; v += kFoldPrepThreads) first[v] = kNone;
+    } else {
+        for (int i = tid; i < nsrc; i += kFoldPrepThreads) {
+            const int s = src[i];
+            if (s >= 0 && s < V) first[rep[s]] = kNone;
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < nsrc; i += kFoldPrepThreads) {
+        const int s = src[i];
+        if (s >= 0 && s < V) atomicMin(&first[rep[s]], i);
+    }
+    __syncthreads();
+    int base = 0;                                // leaders before this chunk
+    for (int i0 = 0; i0 < nsrc; i0 += kFoldPrepThreads) {
+        const int i = i0 + tid;
+        int s = -1, r = -1;
+        if (i < nsrc) {
+            s = src[i];
+            if (s >= 0 && s < V) r = rep[s];
+        }
+        const bool leader = r >= 0 && first[r] == i;
+        const uint64_t m = __ballot(leader);
+        if (lane == 0) wsum[w] = __popcll(m);
+        __syncthreads();
+        int off = base, total = base;
+        for (int k = 0; k < NWV; ++k) {
+            const int c = wsum[k];
+            if (k < w) off += c;
+            total += c;
+        }
+        if (leader) {
+            const int pos = off + lanes_below(m);
+            csrc[pos] = s;
+            slot[r] = pos;
+        }
+        base = total;
+        __syncthreads();                         // wsum is rewritten by the next chunk
+    }
+    for (int i = tid; i < nsrc; i += kFoldPrepThreads) {
+        const int s = src[i];
+        int L = -1, ls = -1;
+        if (s >= 0 && s < V) {
+            const int r = rep[s];
+            L = slot[r];
+            ls = src[first[r]];
+        }
+        lead[i] = L;
+        lsrc[i] = ls;
+        if (i >= base) csrc[i] = -1;
+    }
+    if (tid == 0) count[0] = base;
+}
+
+// a row of `bytes` bytes: 16 bytes per thread and step when vec (row size and
+// both tables 16-byte aligned), else in elements of es (2 or 4) bytes; in ==
+// nullptr fills the row with 0xFF bytes (an empty row in every layout)
+__device__ __forceinline__ void fold_copy_row(const char *__restrict__ in, char *__restrict__ out,
+                                              size_t bytes, int es, bool vec)
+{
+    const int tid = (int)threadIdx.x;
+    constexpr int nt = kFoldDeriveThreads;
+    if (vec) {
+        const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);
+        const uint4 *i4 = reinterpret_cast<const uint4 *>(in);
+        uint4 *o4 = reinterpret_cast<uint4 *>(out);
+        for (size_t k = tid; k < bytes / 16; k += nt) o4[k] = in ? i4[k] : ones;
+    } else if (es == 4) {
+        const uint32_t *i1 = reinterpret_cast<const uint32_t *>(in);
+        uint32_t *o1 = reinterpret_cast<uint32_t *>(out);
+        for (size_t k = tid; k < bytes / 4; k += nt) o1[k] = in ? i1[k] : ~0u;
+    } else {
+        const uint16_t *i1 = reinterpret_cast<const uint16_t *>(in);
+        uint16_t *o1 = reinterpret_cast<uint16_t *>(out);
+        for (size_t k = tid; k < bytes / 2; k += nt) o1[k] = in ? i1[k] : (uint16_t)0xFFFF;
+    }
+}
+
+// one patched entry in the layout's encoding (par < 0: unreached)
+__device__ __forceinline__ void fold_put(int fmt, int hbytes, uint32_t *__restrict__ out0,
+                                         uint32_t *__restrict__ out1, char *__restrict__ outh,
+                                         size_t e, int par, int prt, int slot, int hop)
+{
+    if (fmt == kTreeInt32) {
+        out0[e] = (uint32_t)par;
+        out1[e] = (uint32_t)(par < 0 ? -1 : prt);
+    } else if (par < 0) {
+        out0[e] = 0xFFFFFFFFu;
+    } else if (fmt == kTreePort16) {
+        out0[e] = ((uint32_t)par & 0xFFFFu) | ((uint32_t)prt << 16);
+    } else {
+        out0[e] = (uint32_t)par | ((uint32_t)slot << 26);
+    }
+    if (hbytes == 2) reinterpret_cast<uint16_t *>(outh)[e] = (uint16_t)(par < 0 ? -1 : hop);
+    else if (hbytes == 4) reinterpret_cast<int32_t *>(outh)[e] = par < 0 ? -1 : hop;
+}
+
+// one workgroup per caller row i: the leader's row, then -- for a row that is
+// not its leader's own -- the patched entries, each stored by one thread
+// after the copy (workgroup barrier: the later store to the same word wins).
+// With ls the leader's source and s this row's:
+//   v in row(s)  parent s, the port / slot of s's link to v, hops 1
+//   v == s       the root
+//   v == ls      what the leader's row holds for s, the port / slot that of
+//                the same parent's link to ls (it exists: equal in-rows)
+// The patches are worked out before the copy, so their loads (the last wave
+// looks ls up in the parent's row, a lane per entry) do not queue behind it.
+// fmt: table 0 is int32 parents (table 1 the ports), parent | port << 16, or
+// parent | slot << 26; hbytes: 0 (no hop table), 2 or 4; vec: bit k set when
+// table k (2: hops) takes the 16-byte copy
+__global__ __launch_bounds__(kFoldDeriveThreads) void dfs_fold_derive_kernel(
+    int V, int fmt, int hbytes, int vec, const int32_t *__restrict__ src,
+    const int32_t *__restrict__ lsrc, const int32_t *__restrict__ lead,
+    const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
+    const int32_t *__restrict__ port, const uint32_t *__restrict__ in0,
+    uint32_t *__restrict__ out0, const uint32_t *__restrict__ in1, uint32_t *__restrict__ out1,
+    const char *__restrict__ inh, char *__restrict__ outh)
+{
+    constexpr int kLast = kFoldDeriveThreads - SDNR_WAVE;    // first thread of the last wave
+    const size_t i = blockIdx.x;
+    const int tid = (int)threadIdx.x;
+    const int L = uniform(lead[i]), s = uniform(src[i]), ls = uniform(lsrc[i]);
+    const bool patch = L >= 0 && s != ls;        // else an empty row, or the leader's as it is
+    const size_t ob = i * (size_t)V, lb = (size_t)(L < 0 ? 0 : L) * (size_t)V;
+    int a = 0, d = 0;
+    int av = -1, apar = s, aprt = -1, aslot = 63, ahop = 0;      // row(s) / the root
+    int bv = -1, bpar = -1, bprt = -1, bslot = 63, bhop = -1;    // ls
+    if (patch) {
+        a = row_ptr[s];
+        d = row_ptr[s + 1] - a;
+        if (tid < d) {
+            av = col[a + tid];
+            aprt = port[a + tid];
+            aslot = tid;
+            ahop = 1;
+        } else if (tid == d) {
+            av = s;
+        }
+        if (tid >= kLast) {
+            const int lane = tid - kLast;
+            const uint32_t e = in0[lb + s];
+            const int par = fmt == kTreeInt32 ? (int)e
+                            : e == 0xFFFFFFFFu ? -1
+                            : (int)(e & (fmt == kTreePort16 ? 0xFFFFu : 0x3FFFFFFu));
+            int hop = -1;
+            if (hbytes == 2) hop = reinterpret_cast<const uint16_t *>(inh)[lb + s];
+            else if (hbytes == 4) hop = reinterpret_cast<const int32_t *>(inh)[lb + s];
+            if (par < 0) {
+                if (lane == 0) bv = ls;
+            } else {
+                const int lo = row_ptr[par], n = row_ptr[par + 1] - lo;
+                for (int k = lane; k < n; k += SDNR_WAVE)
+                    if (col[lo + k] == ls) {
+                        bv = ls;
+                        bpar = par;
+                        bprt = port[lo + k];
+                        bslot = k;
+                        bhop = hop;
+                    }
+            }
+        }
+    }
+    fold_copy_row(L < 0 ? nullptr : reinterpret_cast<const char *>(in0 + lb),
+                  reinterpret_cast<char *>(out0 + ob), 4 * (size_t)V, 4, (vec & 1) != 0);
+    if (fmt == kTreeInt32)
+        fold_copy_row(L < 0 ? nullptr : reinterpret_cast<const char *>(in1 + lb),
+                      reinterpret_cast<char *>(out1 + ob), 4 * (size_t)V, 4, (vec & 2) != 0);
+    if (hbytes)
+        fold_copy_row(L < 0 ? nullptr : inh + lb * hbytes, outh + ob * hbytes,
+                      (size_t)hbytes * V, hbytes, (vec & 4) != 0);
+    if (!patch) return;
+    __syncthreads();
+    if (av >= 0) fold_put(fmt, hbytes, out0, out1, outh, ob + av, apar, aprt, aslot, ahop);
+    if (bv >= 0) fold_put(fmt, hbytes, out0, out1, outh, ob + bv, bpar, bprt, bslot, bhop);
+    for (int t = tid + kFoldDeriveThreads; t <= d; t += kFoldDeriveThreads) {   // rows wider than the workgroup
+        if (t < d) fold_put(fmt, hbytes, out0, out1, outh, ob + col[a + t], s, port[a + t], t, 1);
+        else fold_put(fmt, hbytes, out0, out1, outh, ob + s, s, -1, 63, 0);
+    }
+}
+
+// fold this batch?  Only a graph with twins, and by default only above 2.5
+// sources per CU, the measured crossover at k=48 (forced on,
+// 144 / 288 / 516 / 576 sources lose 6.6 / 0.8 / 0.6 us or tie, 720 / 864 /
+// 1,152 gain): below it one launch runs near the single-source chain time
+// and the fold only adds its two launches.  SDNROUTE_DFS_FOLD=0|1 forces it
+// off / on (A/B, tests on tiny batches)
+static bool dfs_fold(const sdnr_ctx *ctx, int nsrc)
+{
+    if (!ctx->has_twins) return false;
+    if (const char *f = getenv("SDNROUTE_DFS_FOLD")) {
+        if (!strcmp(f, "0")) return false;
+        if (!strcmp(f, "1")) return true;
+    }
+    return 2 * (int64_t)nsrc > 5 * (int64_t)ctx->num_cus;
+}
+
+int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
+                    int32_t *d_parent, int32_t *d_port, int32_t *d_hops, uint32_t *d_tree,
+                    bool slots, bool hops16)
+{
+    const int V = ctx->V;
+    ctx->dfs_nsrc = nsrc;
+    ctx->dfs_folded = false;
+    if (nsrc == 0 || V == 0 || !dfs_fold(ctx, nsrc))
+        return dfs_dispatch(ctx, d_src, nsrc, d_parent, d_port, d_hops, d_tree, slots, hops16);
+    const bool packed = d_tree != nullptr;
+    const size_t n = (size_t)nsrc * (size_t)V;
+    const int hbytes = d_hops ? (hops16 ? 2 : 4) : 0;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // scratch3: the searched count, the compacted sources, every position's
+    // leader row and leader, the prep kernel's two class tables, then the
+    // leaders' table set in the caller's layout
+    const size_t o_csrc = 256, o_lead = o_csrc + up(4 * (size_t)nsrc),
+                 o_lsrc = o_lead + up(4 * (size_t)nsrc), o_tab = o_lsrc + up(4 * (size_t)nsrc),
+                 o_t0 = o_tab + up(8 * (size_t)V), o_t1 = o_t0 + up(4 * n),
+                 o_h = o_t1 + (packed ? 0 : up(4 * n)), need = o_h + up((size_t)hbytes * n);
+    if (need > kFoldScratchBytes)
+        return dfs_dispatch(ctx, d_src, nsrc, d_parent, d_port, d_hops, d_tree, slots, hops16);
+    int rc = sdnr_reserve(&ctx->scratch3, &ctx->scratch3_bytes, need);
+    if (rc) return rc;
+    char *sb = static_cast<char *>(ctx->scratch3);
+    int32_t *count = reinterpret_cast<int32_t *>(sb);
+    int32_t *csrc = reinterpret_cast<int32_t *>(sb + o_csrc);
+    int32_t *lead = reinterpret_cast<int32_t *>(sb + o_lead);
+    int32_t *lsrc = reinterpret_cast<int32_t *>(sb + o_lsrc);
+    int32_t *tab = reinterpret_cast<int32_t *>(sb + o_tab);
+    int32_t *t0 = reinterpret_cast<int32_t *>(sb + o_t0);
+    int32_t *t1 = packed ? nullptr : reinterpret_cast<int32_t *>(sb + o_t1);
+    int32_t *th = hbytes ? reinterpret_cast<int32_t *>(sb + o_h) : nullptr;
+    // SDNROUTE_DFS_FOLD_LDS=0 keeps the class tables in global memory (tests)
+    const char *fl = getenv("SDNROUTE_DFS_FOLD_LDS");
+    const bool lds = V <= kFoldLdsMaxV && !(fl && !strcmp(fl, "0"));
+    const bool timed = ctx->timed;
+    if (timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    hipLaunchKernelGGL(dfs_fold_prep_kernel, dim3(1), dim3(kFoldPrepThreads),
+                       lds ? 8 * (size_t)V : 0, ctx->stream, V, nsrc, lds ? 1 : 0, d_src,
+                       ctx->twin_rep, tab, csrc, lead, lsrc, count);
+    SDNR_HIP(hipGetLastError());
+    ctx->timed = false;                          // the span is timed around the three launches
+    rc = dfs_dispatch(ctx, csrc, nsrc, packed ? nullptr : t0, t1, th,
+                      packed ? reinterpret_cast<uint32_t *>(t0) : nullptr, slots, hops16);
+    ctx->timed = timed;
+    if (rc) return rc;
+    uint32_t *o0 = packed ? d_tree : reinterpret_cast<uint32_t *>(d_parent);
+    auto vec_ok = [&](const void *p, size_t row_bytes) {
+        return row_bytes % 16 == 0 && reinterpret_cast<uintptr_t>(p) % 16 == 0;
+    };
+    const int vec = (vec_ok(o0, 4 * (size_t)V) ? 1 : 0) |
+                    (!packed && vec_ok(d_port, 4 * (size_t)V) ? 2 : 0) |
+                    (hbytes && vec_ok(d_hops, (size_t)hbytes * V) ? 4 : 0);
+    hipLaunchKernelGGL(dfs_fold_derive_kernel, dim3(nsrc), dim3(kFoldDeriveThreads), 0,
+                       ctx->stream, V, packed ? (slots ? kTreeSlot : kTreePort16) : kTreeInt32,
+                       hbytes, vec, d_src, lsrc, lead, ctx->row_ptr, ctx->col, ctx->port,
+                       reinterpret_cast<const uint32_t *>(t0), o0,
+                       reinterpret_cast<const uint32_t *>(t1), reinterpret_cast<uint32_t *>(d_port),
+                       reinterpret_cast<const char *>(th), reinterpret_cast<char *>(d_hops));
+    SDNR_HIP(hipGetLastError());
+    ctx->dfs_folded = true;
+    ctx->last_launches = 3;                      // prep, search, derive
+    if (timed) SDNR_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     return SDNR_OK;
 }

@@ -47,7 +47,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_last_kernel_ms", "sdnr_last_kernel", "sdnr_last_launches", "sdnr_last_sweeps",
     "sdnr_edge_ports", "sdnr_dfs_rows_affected", "sdnr_link_loads",
     "sdnr_ecmp_link_loads", "sdnr_graph_costs", "sdnr_cost_tables",
-    "sdnr_cost_ecmp_link_loads",
+    "sdnr_cost_ecmp_link_loads", "sdnr_graph_twin_reps", "sdnr_last_dfs_searched",
 )
 
 
@@ -108,6 +108,8 @@ def _bind(L):
         "sdnr_graph_costs": ([vp, vp], c_int),
         "sdnr_cost_tables": ([vp, vp, i32, vp, vp, vp, u32], c_int),
         "sdnr_cost_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, vp, u32], c_int),
+        "sdnr_graph_twin_reps": ([vp, vp], c_int),
+        "sdnr_last_dfs_searched": ([vp, ctypes.POINTER(i32)], c_int),
     }
     # an A/B build named by SDNROUTE_LIB may predate some entry points: those
     # stay unbound (calling one raises AttributeError); the in-tree library
@@ -576,6 +578,20 @@ class Context(object):
     def last_launches(self):
         n = ctypes.c_int32()
         _check(self._lib.sdnr_last_launches(self._h, ctypes.byref(n)))
+        return n.value
+
+    def twin_reps(self):
+        """rep[V]: the smallest vertex of each vertex's twin class
+        (sdnr_graph_twin_reps)."""
+        rep = np.empty(max(self.V, 0), np.int32)
+        _check(self._lib.sdnr_graph_twin_reps(self._h, _ptr(rep)))
+        return rep
+
+    def last_dfs_searched(self):
+        """Sources the last DFS table call searched: fewer than the batch when
+        it folded twin classes (sdnr_last_dfs_searched)."""
+        n = ctypes.c_int32()
+        _check(self._lib.sdnr_last_dfs_searched(self._h, ctypes.byref(n)))
         return n.value
 
     def last_sweeps(self):

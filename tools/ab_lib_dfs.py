@@ -66,7 +66,8 @@ def main():
         print("opened %s" % p, file=sys.stderr, flush=True)
     res = {p: {} for p in libs}
     only = os.environ.get("AB_NS")            # e.g. "144,1152": these counts only
-    ns = [n for n in (1, 8, 32, 144, 258, 288, 516, 576, 1152, len(srcs)) if n <= len(srcs)]
+    ns = [n for n in (1, 8, 32, 144, 258, 288, 516, 576, 720, 864, 1008, 1152, len(srcs))
+          if n <= len(srcs)]
     if only:
         ns = [n for n in ns if str(n) in only.split(",") or (n == len(srcs) and "all" in only)]
     for n in sorted(set(ns)):
@@ -99,6 +100,11 @@ def main():
         print("done n=%d" % n, file=sys.stderr, flush=True)      # progress (a silent run looks hung)
     for p in libs:
         print(fab, "shortest" if shortest else "dfs", os.path.basename(p), {n: round(float(np.median(v)), 1) for n, v in res[p].items()})
+    for p in libs:                               # the spread: min / median / max, and every repetition
+        for n, v in res[p].items():
+            print("%s %s %s n=%d us min/med/max %.1f / %.1f / %.1f reps %s"
+                  % (fab, "shortest" if shortest else "dfs", os.path.basename(p), n, min(v),
+                     float(np.median(v)), max(v), [round(x, 1) for x in v]))
 
 
 if __name__ == "__main__":
