@@ -439,6 +439,59 @@ int sdnr_cost_ecmp_link_loads(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrow
                               const int64_t *pair_off, const int32_t *srcs,
                               const uint64_t *weight, double *load, uint32_t flags);
 
+/* Link-failure what-if: sdnr_cost_ecmp_link_loads once per failure SCENARIO,
+ * without touching the uploaded graph, its costs or any table.  A scenario is
+ * a set of failed directed links; for every scenario k and destination row r
+ * one workgroup computes the least costs toward dst[r] on the graph without
+ * the scenario's links (pull Bellman-Ford, as sdnr_cost_tables), then orders
+ * the least-cost DAG, counts the routes and pushes the row's demand down it
+ * (as sdnr_cost_ecmp_link_loads), the failed links excluded at every step and
+ * all of it in LDS: no table is written.
+ *   dst        [nrows] the destination (dense id) of row r;
+ *   pair_off, srcs, weight: as in sdnr_cost_ecmp_link_loads; with
+ *              npairs = pair_off[nrows] - pair_off[0], pair i below is
+ *              srcs[pair_off[0] + i];
+ *   scen_off   [nscen + 1] int64: the failed links of scenario k are
+ *              scen_edges[scen_off[k] .. scen_off[k+1]), CSR edge indices in
+ *              [0, E), ascending within a scenario, duplicates allowed
+ *              (scen_edges may be NULL when every scenario is empty);
+ *   load       [nscen][E] double, slice k in the uploaded CSR's edge order.
+ *              The call ADDS into load;
+ *   lost       [nscen] double or NULL: the call ADDS the weight of every pair
+ *              with a source in [0, V), s != d and weight > 0 that has no route
+ *              in scenario k;
+ *   routed     [nscen][npairs] u8 or NULL, WRITTEN for the pairs of every row
+ *              that has pairs: 1 iff the source is in [0, V) and reaches the
+ *              destination in scenario k (the pair s == d counts as routed).
+ * Defining property: slice k equals sdnr_cost_ecmp_link_loads over
+ * sdnr_cost_tables rows of the graph from which the links of scenario k were
+ * really removed, scattered back to this graph's edge order; the links of the
+ * scenario carry exactly 0.  That holds for a failed link that stays TIGHT too
+ * (pcost[n] + cost == pcost[x] still holds for it when x keeps another next
+ * hop of the same cost): it carries nothing and counts as no route.  The costs
+ * are those of sdnr_graph_costs; with none uploaded every link costs 1 and the
+ * routes are the hop-count ECMP routes.  An empty scenario is the fabric as it
+ * is: sdnr_cost_ecmp_link_loads' result (sdnr_ecmp_link_loads' without costs).
+ * Failures are directed: failing x -> n leaves n -> x up.
+ * SDNR_LOADS_SPLIT_HOP, the sums (f64 atomics) and "no NaN or Inf reaches load
+ * or lost" as in sdnr_cost_ecmp_link_loads.  Device pointers only (flags must
+ * hold SDNR_DEVICE_PTRS); asynchronous on the context stream (the ends of
+ * pair_off and scen_off are read back first: not monotone is SDNR_ERR_INVAL);
+ * on a multi-device context it runs on the primary device; SDNR_TIMING as in
+ * sdnr_ecmp_link_loads.  Without an uploaded graph: SDNR_ERR_STATE.  Negative
+ * counts or NULL where a buffer is required: SDNR_ERR_INVAL.  nscen == 0,
+ * nrows == 0 or no pairs: SDNR_OK, nothing touched.  A destination outside
+ * [0, V) is an empty row: nothing added, its pairs not routed.  One launch.
+ * A failed-link index outside [0, E) (that entry is ignored), a scenario that
+ * is not ascending, offsets outside their lists, relaxation sweeps that outrun
+ * V and a route count above the double range are reported by sdnr_synchronize
+ * as SDNR_ERR_INVAL. */
+int sdnr_failure_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *dst, int32_t nrows,
+                                 const int64_t *pair_off, const int32_t *srcs,
+                                 const uint64_t *weight, int32_t nscen, const int64_t *scen_off,
+                                 const int32_t *scen_edges, double *load, double *lost,
+                                 uint8_t *routed, uint32_t flags);
+
 /* Flood ports (TopologyManager._is_edge_port / _do_broadcast, reference
  * sdnmpi/topology.py:150-177): is_edge[i] = 1 iff ports[i] is neither end of
  * any link.  Keys are (dense switch id << 32) | port_no; ends (both ends of

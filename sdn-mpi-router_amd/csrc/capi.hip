@@ -68,6 +68,11 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "(a vertex of finite cost > 0 without a next hop, an ordering pass "
                              "longer than V, a route count above the double range) or pair_off is "
                              "not monotone: loads invalid");
+        if (h & kErrFailureLoads)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: a failed-link index "
+                             "outside [0, E) (ignored), a scenario list that is not ascending, "
+                             "pair_off or scen_off outside their lists, relaxation sweeps that "
+                             "outran V or a route count above the double range: loads invalid");
         if (h & kErrCostTables)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_tables: V relaxation sweeps did not reach "
                              "the fixed point (link costs outside what sdnr_graph_costs accepts): "
@@ -1379,6 +1384,57 @@ int sdnr_cost_ecmp_link_loads(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrow
     ctx->timed = (flags & SDNR_TIMING) != 0;
     return sdnr_launch_cost_ecmp_link_loads(ctx, pcost, nrows, pair_off, lo, hi, srcs, weight,
                                             load, (flags & SDNR_LOADS_SPLIT_HOP) != 0);
+}
+
+// *lo, *hi = off[0], off[n] of a device int64 offset list
+static int fetch_bounds(sdnr_ctx *ctx, const int64_t *off, int32_t n, int64_t *lo, int64_t *hi)
+{
+    int w[4];
+    int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(off), 2, w);
+    if (!rc) rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(off + n), 2, w + 2);
+    if (rc) return rc;
+    *lo = (int64_t)(((uint64_t)(uint32_t)w[1] << 32) | (uint32_t)w[0]);
+    *hi = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
+    return SDNR_OK;
+}
+
+int sdnr_failure_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *dst, int32_t nrows,
+                                 const int64_t *pair_off, const int32_t *srcs,
+                                 const uint64_t *weight, int32_t nscen, const int64_t *scen_off,
+                                 const int32_t *scen_edges, double *load, double *lost,
+                                 uint8_t *routed, uint32_t flags)
+{
+    CHECK_CTX(ctx);
+    if (ctx->V < 0)
+        return sdnr_fail(SDNR_ERR_STATE, "sdnr_failure_ecmp_link_loads: no graph uploaded");
+    if (!(flags & SDNR_DEVICE_PTRS))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: device pointers only");
+    if (nrows < 0 || nscen < 0)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: negative count");
+    if (nrows == 0 || nscen == 0) return SDNR_OK;
+    if (!dst || !pair_off || !scen_off || !load)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: null pointer");
+    SDNR_HIP(hipSetDevice(ctx->device));
+    // the bounds of the pair list and of the failed-link list
+    int64_t lo, hi, flo, fhi;
+    int rc = fetch_bounds(ctx, pair_off, nrows, &lo, &hi);
+    if (!rc) rc = fetch_bounds(ctx, scen_off, nscen, &flo, &fhi);
+    if (rc) return rc;
+    if (lo < 0 || hi < lo)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: pair_off not monotone "
+                         "(pair_off[0]=%lld, pair_off[%d]=%lld)", (long long)lo, nrows,
+                         (long long)hi);
+    if (flo < 0 || fhi < flo)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: scen_off not monotone "
+                         "(scen_off[0]=%lld, scen_off[%d]=%lld)", (long long)flo, nscen,
+                         (long long)fhi);
+    if (hi == lo || ctx->V == 0) return SDNR_OK;
+    if (!srcs || (fhi > flo && !scen_edges))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: null pointer");
+    ctx->timed = (flags & SDNR_TIMING) != 0;
+    return sdnr_launch_failure_ecmp_link_loads(ctx, dst, nrows, pair_off, lo, hi, srcs, weight,
+                                               nscen, scen_off, flo, fhi, scen_edges, load, lost,
+                                               routed, (flags & SDNR_LOADS_SPLIT_HOP) != 0);
 }
 
 int sdnr_apsp(sdnr_ctx *ctx, uint16_t *dist, uint32_t flags)

@@ -211,6 +211,16 @@ constexpr int kErrCostEcmpLoads = 32768; // sdnr_cost_ecmp_link_loads: a pcost r
 constexpr int kCostEcmpBytesPerV = 22;
 constexpr int kCostEcmpLdsMaxV = SDNR_LDS_PER_CU / kCostEcmpBytesPerV / 100 * 100;
 static_assert(kCostEcmpLdsMaxV == 7400 && kCostEcmpLdsMaxV < 0xFFFF, "depths in LDS are u16");
+constexpr int kErrFailureLoads = 65536; // sdnr_failure_ecmp_link_loads: a bad failed-link list / bad offsets / sweeps past V
+
+// sdnr_failure_ecmp_link_loads keeps a (scenario, row) item's route counts,
+// flows, costs, depths and failed-link flags in LDS (23 bytes per vertex) up to
+// this V -- what the CU's LDS holds, rounded down to a hundred: 7,100, 163,300
+// of 163,840 bytes --, else all of them in global scratch (u32 depths: 25
+// bytes per vertex and workgroup, at most kLoadsScratchBytes in all)
+constexpr int kFailureBytesPerV = 23;
+constexpr int kFailureLdsMaxV = SDNR_LDS_PER_CU / kFailureBytesPerV / 100 * 100;
+static_assert(kFailureLdsMaxV == 7100 && kFailureLdsMaxV < 0xFFFF, "depths in LDS are u16");
 
 // error plumbing (capi.hip)
 int sdnr_fail(int code, const char *fmt, ...);
@@ -292,5 +302,15 @@ int sdnr_launch_cost_ecmp_link_loads(sdnr_ctx *ctx, const uint32_t *d_pcost, int
                                      const int64_t *d_pair_off, int64_t pair_lo, int64_t pair_hi,
                                      const int32_t *d_srcs, const uint64_t *d_weight,
                                      double *d_load, bool hop);
+// ... once per failure scenario, the scenario's links masked out (failure_loads.hip);
+// scen_lo / scen_hi = scen_off[0] / scen_off[nscen]
+int sdnr_launch_failure_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *d_dst, int32_t nrows,
+                                        const int64_t *d_pair_off, int64_t pair_lo,
+                                        int64_t pair_hi, const int32_t *d_srcs,
+                                        const uint64_t *d_weight, int32_t nscen,
+                                        const int64_t *d_scen_off, int64_t scen_lo,
+                                        int64_t scen_hi, const int32_t *d_scen_edges,
+                                        double *d_load, double *d_lost, uint8_t *d_routed,
+                                        bool hop);
 int sdnr_launch_edge_ports(sdnr_ctx *ctx, const uint64_t *d_ends, int32_t nends,
                            const uint64_t *d_ports, int32_t nports, uint8_t *d_is_edge);

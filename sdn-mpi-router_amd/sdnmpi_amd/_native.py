@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_edge_ports", "sdnr_dfs_rows_affected", "sdnr_link_loads",
     "sdnr_ecmp_link_loads", "sdnr_graph_costs", "sdnr_cost_tables",
     "sdnr_cost_ecmp_link_loads", "sdnr_graph_twin_reps", "sdnr_last_dfs_searched",
+    "sdnr_failure_ecmp_link_loads",
 )
 
 
@@ -108,6 +109,8 @@ def _bind(L):
         "sdnr_graph_costs": ([vp, vp], c_int),
         "sdnr_cost_tables": ([vp, vp, i32, vp, vp, vp, u32], c_int),
         "sdnr_cost_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, vp, u32], c_int),
+        "sdnr_failure_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, u32],
+                                         c_int),
         "sdnr_graph_twin_reps": ([vp, vp], c_int),
         "sdnr_last_dfs_searched": ([vp, ctypes.POINTER(i32)], c_int),
     }
@@ -496,6 +499,25 @@ class Context(object):
             ctypes.c_void_p(srcs_ptr) if srcs_ptr else None,
             ctypes.c_void_p(weight_ptr) if weight_ptr else None,
             ctypes.c_void_p(load_ptr) if load_ptr else None, flags))
+
+    def failure_ecmp_link_loads_device(self, dst_ptr, nrows, pair_off_ptr, srcs_ptr, weight_ptr,
+                                       nscen, scen_off_ptr, scen_edges_ptr, load_ptr, lost_ptr=0,
+                                       routed_ptr=0, hop=False, timing=False):
+        """Add the ECMP-over-least-cost link loads of a demand once per failure
+        scenario into ``load`` (f64 [nscen][E]; the caller zeroes it), the
+        scenario's links (CSR edge indices ``scen_edges[scen_off[k] ..
+        scen_off[k+1])``, ascending) masked out; ``lost`` (f64 [nscen], added
+        into) and ``routed`` (u8 [nscen][npairs], written) may be 0:
+        sdnr_failure_ecmp_link_loads, device pointers, asynchronous.  Row r
+        routes toward dense switch ``dst[r]`` under the costs in force (none
+        uploaded: every link costs 1).  ``weight_ptr`` 0: every pair weighs 1;
+        ``hop``: split evenly per switch (SDNR_LOADS_SPLIT_HOP)."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_SPLIT_HOP if hop else 0)
+        p = lambda a: ctypes.c_void_p(a) if a else None    # noqa: E731
+        _check(self._lib.sdnr_failure_ecmp_link_loads(
+            self._h, p(dst_ptr), int(nrows), p(pair_off_ptr), p(srcs_ptr), p(weight_ptr),
+            int(nscen), p(scen_off_ptr), p(scen_edges_ptr), p(load_ptr), p(lost_ptr),
+            p(routed_ptr), flags))
 
     def apsp(self):
         dist = np.empty((self.V, self.V), np.uint16)

@@ -44,7 +44,8 @@ __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "sp_row_bytes", "link_loads_host", "ecmp_link_loads_host", "cost_tables_host",
            "check_link_costs", "COST_INF", "COST_MAX", "COST_LDS_MAX_V", "COST_LDS_B8_MAX_V",
            "cost_ecmp_link_loads_host", "least_cost_paths_lex", "count_least_cost_paths",
-           "COST_ECMP_LDS_MAX_V"]
+           "COST_ECMP_LDS_MAX_V", "FAILURE_LDS_MAX_V", "normalise_scenarios",
+           "failure_ecmp_link_loads_host"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -559,6 +560,77 @@ def cost_ecmp_link_loads_host(csr, cost, pcost, rows, srcs, weights=None, split=
     return load
 
 
+FAILURE_LDS_MAX_V = 7100        # csrc/common.h kFailureLdsMaxV: what-if row state in LDS
+
+
+def normalise_scenarios(scenarios, E):
+    """Failure scenarios (a sequence of int arrays of CSR edge indices) as the
+    list of their sorted, deduplicated int32 arrays; an index outside [0, E)
+    is a ValueError."""
+    out = []
+    for sc in scenarios:
+        a = np.unique(np.asarray(sc, np.int64).reshape(-1))
+        if a.size and (a[0] < 0 or a[-1] >= E):
+            raise ValueError("a failed link is an edge index in [0, %d)" % E)
+        out.append(a.astype(np.int32))
+    return out
+
+
+def failure_ecmp_link_loads_host(csr, cost, dsts, rows, srcs, weights=None, scenarios=(),
+                                 split="route"):
+    """numpy restatement of sdnr_failure_ecmp_link_loads (the CPU tests' engine
+    double and an independent check of failure_loads.hip): (load float64
+    [nscen, E], lost float64 [nscen], routed bool [nscen, npairs]) of pairs
+    (toward dense switch ``dsts[rows[i]]``, from ``srcs[i]``, weight
+    ``weights[i]`` or 1) split over every least-cost route under the link costs
+    ``cost`` (uint32 [E]; None: every link costs 1), once per scenario of
+    ``scenarios`` (int arrays of failed CSR edge indices) with that scenario's
+    links down.
+
+    Deliberately not the kernel's masking: per scenario the failed edges are
+    really removed from the CSR, ``cost_tables_host`` and
+    ``cost_ecmp_link_loads_host`` run on the reduced graph, and the loads are
+    scattered back to the full graph's edge order (a failed link holds 0.0).
+    ``routed[k, i]``: the source is a vertex and reaches the destination in
+    scenario k (s == d counts); ``lost[k]``: the weight of the pairs with s !=
+    d and weight > 0 whose source is a vertex that does not."""
+    from .topologies import CSR
+    if split not in SPLITS:
+        raise ValueError("split must be 'route' or 'hop'")
+    V, E = int(csr.V), int(csr.E)
+    cost = np.ones(E, np.uint32) if cost is None else check_link_costs(csr, cost)
+    scen = normalise_scenarios(scenarios, E)
+    dsts = np.asarray(dsts, np.int64)
+    rows = np.asarray(rows, np.int64)
+    srcs = np.asarray(srcs, np.int64)
+    n = int(rows.shape[0])
+    w = np.ones(n, np.uint64) if weights is None else np.asarray(weights, np.uint64)
+    load = np.zeros((len(scen), E), np.float64)
+    lost = np.zeros(len(scen), np.float64)
+    routed = np.zeros((len(scen), n), bool)
+    if n == 0 or dsts.size == 0:
+        return load, lost, routed
+    if rows.min() < 0 or rows.max() >= dsts.shape[0]:
+        raise ValueError("failure_ecmp_link_loads_host: a pair names a row outside dsts")
+    esrc = np.repeat(np.arange(V, dtype=np.int64), np.diff(np.asarray(csr.row_ptr, np.int64)))
+    d = dsts[rows]
+    s_ok = (srcs >= 0) & (srcs < V)
+    d_ok = (d >= 0) & (d < V)
+    sc = np.where(s_ok, srcs, 0)
+    for k, failed in enumerate(scen):
+        keep = np.ones(E, bool)
+        keep[failed] = False
+        rp = np.zeros(V + 1, np.int64)
+        np.cumsum(np.bincount(esrc[keep], minlength=V), out=rp[1:])
+        red = CSR(csr.dpids, rp, np.asarray(csr.col)[keep], np.asarray(csr.port)[keep])
+        pc = cost_tables_host(red, cost[keep], dsts)[0]
+        load[k, keep] = cost_ecmp_link_loads_host(red, cost[keep], pc, rows, srcs, weights, split)
+        routed[k] = s_ok & d_ok & (pc[rows, sc] != COST_INF)
+        gone = s_ok & (srcs != d) & (w > 0) & ~routed[k]
+        lost[k] = float(w[gone].astype(np.float64).sum())
+    return load, lost, routed
+
+
 class RouteEngine(object):
     """The GPU route engine of one TopologyDB: HIP device ``device`` (int),
     or the devices of a list (single-process multi-GPU, sources sharded over
@@ -974,6 +1046,83 @@ class RouteEngine(object):
                                              load.data_ptr(), hop=split == "hop", timing=timing)
         self.ctx.synchronize()              # raises if a row was no least-cost labelling
         return load.cpu().numpy()
+
+    def failure_ecmp_link_loads(self, export, cost, dsts, rows, srcs, weights=None,
+                                scenarios=(), split="route", timing=False):
+        """Link-failure what-if (failure_loads.hip,
+        sdnr_failure_ecmp_link_loads): the loads of ``cost_ecmp_link_loads``
+        once per failure scenario, nothing uploaded or cached changing: (load
+        float64 [nscen, E] in the CSR's edge order, lost float64 [nscen],
+        routed bool [nscen, npairs]) on the host.
+
+        ``cost``: uint32 [E] link costs, or None for unit costs (the context's
+        costs are then cleared: hop-count ECMP); ``dsts``: the dense
+        destination switch of each row; pair i goes from ``srcs[i]`` toward
+        ``dsts[rows[i]]`` and weighs ``weights[i]`` (u64, None: 1).
+        ``scenarios``: a list of int arrays of failed CSR edge indices; they are
+        sorted and deduplicated here (``normalise_scenarios``).  ``lost[k]``:
+        the weight that has no route in scenario k (as double); ``routed[k,
+        i]``: pair i has one (s == d counts).  ``split`` as in
+        ``ecmp_link_loads``.  One launch for all scenarios and rows; sums are
+        f64 atomics: equal to ``failure_ecmp_link_loads_host`` within rounding,
+        not bit-reproducible."""
+        if split not in SPLITS:
+            raise ValueError("split must be 'route' or 'hop'")
+        if cost is None:
+            self.load(export)
+            if self._costs is not None:
+                self._costs = None
+                self.ctx.set_link_costs(None)
+        else:
+            self.set_link_costs(export, cost)
+        t = self._torch
+        V, E = int(export.csr.V), int(export.csr.E)
+        scen = normalise_scenarios(scenarios, E)
+        nscen = len(scen)
+        rows = np.asarray(rows, np.int64)
+        n = int(rows.shape[0])
+        d = np.asarray(dsts, np.int64)
+        nrows = int(d.shape[0])
+        load = np.zeros((nscen, E), np.float64)
+        lost = np.zeros(nscen, np.float64)
+        routed = np.zeros((nscen, n), bool)
+        if n == 0 or nrows == 0 or nscen == 0 or V == 0:
+            return load, lost, routed
+        if rows.min() < 0 or rows.max() >= nrows:
+            raise ValueError("failure_ecmp_link_loads: a pair names a row outside dsts")
+        order, off = _pairs_by_row(rows, nrows)
+        s = np.asarray(srcs, np.int64)[order]
+        s = np.where((s < 0) | (s >= V), -1, s).astype(np.int32)
+        d = np.where((d < 0) | (d >= V), -1, d).astype(np.int32)
+        soff = np.zeros(nscen + 1, np.int64)
+        np.cumsum([a.shape[0] for a in scen], out=soff[1:])
+        edges = np.concatenate(scen + [np.zeros(1, np.int32)]).astype(np.int32)
+        d_dst = t.from_numpy(d).to(self.dev)
+        d_off = t.from_numpy(off).to(self.dev)
+        d_src = t.from_numpy(s).to(self.dev)
+        d_soff = t.from_numpy(soff).to(self.dev)
+        d_edges = t.from_numpy(edges).to(self.dev)
+        d_w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights, np.uint64)[order])
+            d_w = t.from_numpy(w.view(np.int64)).to(self.dev)
+        d_load = t.zeros((nscen, max(E, 1)), dtype=t.float64, device=self.dev)
+        d_lost = t.zeros(nscen, dtype=t.float64, device=self.dev)
+        d_routed = t.zeros((nscen, n), dtype=t.uint8, device=self.dev)
+        self._ready()
+        self.ctx.failure_ecmp_link_loads_device(
+            d_dst.data_ptr(), nrows, d_off.data_ptr(), d_src.data_ptr(),
+            d_w.data_ptr() if d_w is not None else 0, nscen, d_soff.data_ptr(),
+            d_edges.data_ptr(), d_load.data_ptr(), d_lost.data_ptr(), d_routed.data_ptr(),
+            hop=split == "hop", timing=timing)
+        self.ctx.synchronize()              # raises on a bad scenario list
+        load = d_load[:, :E].cpu().numpy()
+        got = d_routed.cpu().numpy().astype(bool)
+        if isinstance(order, slice):
+            routed = got
+        else:
+            routed[:, order] = got
+        return load, d_lost.cpu().numpy(), routed
 
     def edge_ports(self, ends, ports):
         """Flood-port mask (sdnr_edge_ports, reference topology.py:150-155):

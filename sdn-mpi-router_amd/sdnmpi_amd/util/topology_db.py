@@ -37,7 +37,8 @@ try:   # the reference takes OFPP_LOCAL from Ryu's OpenFlow 1.0 module (:5)
 except Exception:   # noqa: BLE001 - Ryu is not a dependency of the engine
     OFPP_LOCAL = 0xfffe
 
-__all__ = ["TopologyDB", "LinkLoads", "SplitLinkLoads", "OFPP_LOCAL", "sdn_mpi_mac"]
+__all__ = ["TopologyDB", "LinkLoads", "SplitLinkLoads", "FailureLoads", "OFPP_LOCAL",
+           "sdn_mpi_mac"]
 
 _INF = 0xFFFF
 _U64 = (1 << 64) - 1
@@ -117,6 +118,54 @@ class SplitLinkLoads(LinkLoads):
         np.add.at(total, self._esrc, self.load)
         np.add.at(total, self._hsw, self.host_load.astype(np.float64))
         return self._dpids, total
+
+
+class FailureLoads(object):
+    """Predicted traffic per link under each of a list of link-failure
+    scenarios (:meth:`TopologyDB.failure_link_loads`).
+
+    ``scenarios``: the scenarios as they were applied -- per scenario the tuple
+    of its directed links ``(src_dpid, dst_dpid)`` that exist, in the CSR's
+    link order, each once.  ``load``: float64 [nscen, E], row k the link loads
+    of scenario k in the order of :class:`LinkLoads`' records (a failed link
+    holds exactly 0.0).  ``lost``: uint64 [nscen], the weight that has no route
+    in scenario k, exact.  ``base``: the :class:`SplitLinkLoads` of the intact
+    fabric."""
+
+    def __init__(self, scenarios, load, lost, base, hkey, hload, result):
+        self.scenarios = scenarios
+        self.load = load
+        self.lost = lost
+        self.base = base
+        self._hkey, self._hload, self._result = hkey, hload, result
+
+    def __len__(self):
+        return len(self.scenarios)
+
+    def scenario(self, i):
+        """The :class:`SplitLinkLoads` of scenario ``i``: its link loads, and
+        the last hops of the pairs that still have a route."""
+        if not 0 <= i < len(self.scenarios):
+            raise IndexError("no scenario %r" % (i,))
+        return self._result(self.load[i], self._hkey, self._hload[i])
+
+    def worst(self):
+        """(load float64 [E], scenario int64 [E]): per link the largest load
+        over the scenarios and the first scenario that attains it (0.0 and -1
+        without scenarios)."""
+        if not len(self.scenarios):
+            E = self.load.shape[1]
+            return np.zeros(E, np.float64), np.full(E, -1, np.int64)
+        return self.load.max(0), self.load.argmax(0).astype(np.int64)
+
+    def worst_dict(self):
+        """{(dpid, out_port): (load, scenario index)} of :meth:`worst` over the
+        links whose largest load is nonzero."""
+        top, at = self.worst()
+        nz = np.nonzero(top)[0]
+        return {(d, p): (x, k) for d, p, x, k in
+                zip(self.base.src_dpid[nz].tolist(), self.base.port[nz].tolist(),
+                    top[nz].tolist(), at[nz].tolist())}
 
 
 def _weights(weights, n):
@@ -666,17 +715,15 @@ class TopologyDB(object):
         return cls(dp, esrc, np.asarray(csr.col, np.int64), np.asarray(csr.port, np.int64),
                    load, hkey[:, 0], hkey[:, 1], hload)
 
-    def _pair_loads(self, pairs, weights, switch_loads, cls):
-        """The MAC-pair form shared by :meth:`link_loads` and
-        :meth:`ecmp_link_loads`: the pairs are resolved to switches, summed to
-        switch pairs, handed to ``switch_loads(ex, sv, dv, w)`` -> (load [E],
-        reach bool per switch pair), and the last hops -- (destination
-        switch, host port or OFPP_LOCAL) of the pairs whose route exists --
-        are added."""
+    def _switch_pairs(self, ex, pairs, weights):
+        """MAC pairs resolved to switches and summed to switch pairs: (w u64
+        per pair, dv, last -- destination switch and last-hop port per pair --,
+        ok -- the pairs whose hosts are known --, inv -- the switch pair of
+        each of those --, and the switch pairs' dense sources, destinations
+        and summed weights)."""
         pairs = list(pairs)
         n = len(pairs)
         w = _weights(weights, n)
-        ex = self.graph()
         V = int(ex.csr.V)
         sv = np.full(n, -1, np.int64)
         dv = np.full(n, -1, np.int64)
@@ -693,7 +740,18 @@ class TopologyDB(object):
         skey, inv = np.unique(sv[ok] * max(1, V) + dv[ok], return_inverse=True)
         sw = np.zeros(skey.shape[0], np.uint64)
         np.add.at(sw, inv, w[ok])
-        load, reach = switch_loads(ex, skey // max(1, V), skey % max(1, V), sw)
+        return w, dv, last, ok, inv, skey // max(1, V), skey % max(1, V), sw
+
+    def _pair_loads(self, pairs, weights, switch_loads, cls):
+        """The MAC-pair form shared by :meth:`link_loads` and
+        :meth:`ecmp_link_loads`: the pairs are resolved to switches, summed to
+        switch pairs, handed to ``switch_loads(ex, sv, dv, w)`` -> (load [E],
+        reach bool per switch pair), and the last hops -- (destination
+        switch, host port or OFPP_LOCAL) of the pairs whose route exists --
+        are added."""
+        ex = self.graph()
+        w, dv, last, ok, inv, ssv, sdv, sw = self._switch_pairs(ex, pairs, weights)
+        load, reach = switch_loads(ex, ssv, sdv, sw)
         got = ok[reach[inv]] if ok.size else ok              # pairs whose route exists
         hkey, hinv = np.unique(np.stack([dv[got], last[got]], 1), axis=0, return_inverse=True)
         hload = np.zeros(hkey.shape[0], np.uint64)
@@ -1147,6 +1205,162 @@ class TopologyDB(object):
         :meth:`mpi_link_loads`)."""
         pairs, weights = self._rank_pairs(rank_to_mac, traffic)
         return self.least_cost_ecmp_link_loads(pairs, weights, split)
+
+    # -- link-failure what-if ---------------------------------------------
+    @staticmethod
+    def cable(a, b):
+        """Both directions of the cable between switches ``a`` and ``b``, for
+        a failure scenario."""
+        return ((a, b), (b, a))
+
+    def switch_links(self, dpid):
+        """Every link into or out of switch ``dpid``, for a failure scenario.
+        Failing them isolates the switch from the fabric; the switch itself
+        stays, so two hosts on it still reach each other."""
+        out = [(dpid, v) for v in sorted(self.links.get(dpid, {}))]
+        out += [(u, dpid) for u in sorted(self.links) if u != dpid and dpid in self.links[u]]
+        return tuple(out)
+
+    def cable_failures(self):
+        """One scenario per connected unordered switch pair -- the N-1 set --
+        ascending: each holds the directions of that cable that exist."""
+        cables = {}
+        for u, nbrs in self.links.items():
+            for v in nbrs:
+                cables.setdefault((min(u, v), max(u, v)), []).append((u, v))
+        return [tuple(sorted(cables[k])) for k in sorted(cables)]
+
+    def _failure_edges(self, ex, failures):
+        """(scenarios, edges): per scenario the tuple of its existing directed
+        links, each once, in CSR order, and their CSR edge indices (int32)."""
+        rp, col = ex.csr.row_ptr, ex.csr.col
+        dp = ex.csr.dpids
+        esrc = None
+        scen, edges = [], []
+        for sc in failures:
+            es = set()
+            for a, b in sc:
+                u, v = ex.index.get(a), ex.index.get(b)
+                if u is None or v is None:
+                    continue
+                lo, hi = int(rp[u]), int(rp[u + 1])
+                e = lo + int(np.searchsorted(col[lo:hi], v))
+                if e < hi and int(col[e]) == v:
+                    es.add(e)
+            es = np.asarray(sorted(es), np.int32)
+            if esrc is None and es.size:
+                esrc = np.repeat(np.arange(ex.csr.V), np.diff(np.asarray(rp, np.int64)))
+            scen.append(tuple((int(dp[esrc[e]]), int(dp[col[e]])) for e in es.tolist()))
+            edges.append(es)
+        return scen, edges
+
+    def _failure_switch_loads(self, ex, edges, sv, dv, w, split):
+        """(load float64 [nscen, E], routed bool [nscen, n]) of switch pairs
+        (dense ids sv -> dv, weights w u64) per failure scenario: one
+        sdnr_failure_ecmp_link_loads call per chunk of scenarios whose load
+        and routed planes fit the table budget."""
+        if split not in ("route", "hop"):
+            raise ValueError("split must be 'route' or 'hop'")
+        E, n = int(ex.csr.E), int(sv.shape[0])
+        load = np.zeros((len(edges), E), np.float64)
+        routed = np.zeros((len(edges), n), bool)
+        if n == 0 or not edges:
+            return load, routed
+        dsts, rows = np.unique(dv, return_inverse=True)
+        budget = DEFAULT_TABLE_BUDGET if self._budget is None else self._budget
+        step = max(1, int(budget) // max(1, 8 * E + n))
+        cost = self._cost_vector(ex)
+        for c0 in range(0, len(edges), step):
+            got = self.engine.failure_ecmp_link_loads(ex, cost, dsts, rows.reshape(-1), sv, w,
+                                                      edges[c0:c0 + step], split)
+            load[c0:c0 + step], routed[c0:c0 + step] = got[0], got[2]
+        return load, routed
+
+    def failure_link_loads(self, failures, pairs, weights=None, split="route"):
+        """What every link carries if links go down: :meth:`least_cost_ecmp_
+        link_loads` of the pairs once per scenario of ``failures``, as a
+        :class:`FailureLoads`.  A scenario is an iterable of directed links
+        ``(src_dpid, dst_dpid)`` (the keys of :meth:`set_link_cost`; see
+        :meth:`cable`, :meth:`switch_links`, :meth:`cable_failures`); links
+        that do not exist are ignored, repeated ones count once, the empty
+        scenario is the fabric as it is.  The routes are the least-cost ECMP
+        sets under the costs in force -- with no cost set,
+        ``find_route(multiple=True)``'s.
+
+        Defining property: ``failure_link_loads(F, pairs, w, split).scenario(k)
+        .as_dict()`` equals ``least_cost_ecmp_link_loads(pairs, w, split)
+        .as_dict()`` of a second ``TopologyDB`` with the same switches, hosts,
+        links and costs on which every link of ``F[k]`` was really removed
+        with ``delete_link`` -- within rounding, and exactly where every share
+        is a power of two.  A failed link carries exactly 0.0, also one that
+        would still lie on a least-cost route by its cost.  A pair that loses
+        every route contributes nothing to scenario k, not its last hop
+        either, and its weight is counted in ``lost[k]``.
+
+        Nothing of this object changes: not ``links``, the export, the cached
+        tables, the costs or the graph on the GPU.  One kernel
+        (failure_loads.hip) recomputes the least costs of every (scenario,
+        destination switch) with the scenario's links masked out and pushes
+        the demand down the surviving least-cost DAG; scenarios are processed
+        in chunks whose results fit the table budget."""
+        pairs = list(pairs)
+        weights = None if weights is None else list(weights)
+        ex = self.graph()
+        scen, edges = self._failure_edges(ex, failures)
+        w, dv, last, ok, inv, ssv, sdv, sw = self._switch_pairs(ex, pairs, weights)
+        load, routed = self._failure_switch_loads(ex, edges, ssv, sdv, sw, split)
+        hkey, hinv = np.unique(np.stack([dv[ok], last[ok]], 1), axis=0, return_inverse=True)
+        hkey, hinv = hkey.reshape(-1, 2), hinv.reshape(-1)
+        hload = np.zeros((len(scen), hkey.shape[0]), np.uint64)
+        lost = np.zeros(len(scen), np.uint64)
+        for k in range(len(scen)):
+            got = routed[k][inv] if ok.size else np.zeros(0, bool)
+            np.add.at(hload[k], hinv[got], w[ok][got])
+            lost[k] = w[ok][~got].sum(dtype=np.uint64)
+        base = self.least_cost_ecmp_link_loads(pairs, weights, split)
+        return FailureLoads(
+            scen, load, lost, base, hkey, hload,
+            lambda ld, hk, hl: self._link_loads_result(ex, ld, hk, hl, SplitLinkLoads))
+
+    def all_pairs_failure_link_loads(self, failures, split="route"):
+        """:meth:`failure_link_loads` over every ordered pair of distinct
+        hosts with weight 1, from the per-switch host counts (as
+        :meth:`all_pairs_link_loads`)."""
+        if any(self._mac_to_int(m) in self.switches for m in self.hosts):
+            macs = list(self.hosts)
+            return self.failure_link_loads(
+                failures, [(a, b) for a in macs for b in macs if a != b], None, split)
+        ex = self.graph()
+        scen, edges = self._failure_edges(ex, failures)
+        hv = np.asarray(self._host_vertices(ex), np.int64)
+        hc = np.asarray(ex.host_count, np.int64)
+        n = hv.shape[0]
+        sv, dv = np.repeat(hv, n), np.tile(hv, n)
+        w = (hc[sv] * (hc[dv] - (sv == dv))).astype(np.uint64)
+        load, routed = self._failure_switch_loads(ex, edges, sv, dv, w, split)
+        hd = np.asarray([ex.index[h.port.dpid] for h in self.hosts.values()], np.int64)
+        hp = np.asarray([int(h.port.port_no) for h in self.hosts.values()], np.int64)
+        hkey, hinv = np.unique(np.stack([hd, hp], 1).reshape(-1, 2), axis=0, return_inverse=True)
+        hkey, hinv = hkey.reshape(-1, 2), hinv.reshape(-1)
+        hload = np.zeros((len(scen), hkey.shape[0]), np.uint64)
+        lost = np.zeros(len(scen), np.uint64)
+        for k in range(len(scen)):
+            # hosts that reach switch d: every host on d gets that many flows, less itself
+            cnt = (routed[k].reshape(n, n) * hc[hv][:, None]).sum(0)
+            into = np.zeros(int(ex.csr.V), np.int64)
+            into[hv] = cnt - 1
+            np.add.at(hload[k], hinv, into[hd].astype(np.uint64))
+            lost[k] = w[~routed[k]].sum(dtype=np.uint64)
+        base = self.all_pairs_least_cost_ecmp_link_loads(split)
+        return FailureLoads(
+            scen, load, lost, base, hkey, hload,
+            lambda ld, hk, hl: self._link_loads_result(ex, ld, hk, hl, SplitLinkLoads))
+
+    def mpi_failure_link_loads(self, failures, rank_to_mac, traffic=None, split="route"):
+        """:meth:`failure_link_loads` of an MPI job (``traffic`` as in
+        :meth:`mpi_link_loads`)."""
+        pairs, weights = self._rank_pairs(rank_to_mac, traffic)
+        return self.failure_link_loads(failures, pairs, weights, split)
 
     def find_routes(self, pairs, multiple=False):
         """find_route over many (src_mac, dst_mac) pairs; tables are computed
