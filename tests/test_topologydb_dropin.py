@@ -185,7 +185,9 @@ class _FakeEngine(object):
         for r, s in zip(rows, srcs):
             d = int(np.nonzero(dist[r] == 0)[0][0])
             q = shortest_paths_lex(c.row_ptr, c.col, dist[r], int(s), d)
-            out.append(np.asarray(q, np.int32).reshape(len(q), -1))
+            # no shortest route: the empty set (find_route(..., True) returns [])
+            out.append(np.asarray(q, np.int32).reshape(len(q), -1) if q
+                       else np.zeros((0, 0), np.int32))
         return out
 
     def edge_ports(self, ends, ports):
