@@ -52,6 +52,10 @@ extern "C" {
 #define SDNR_LOADS_SPLIT_HOP 0x10u /* sdnr_ecmp_link_loads: every switch splits
                                  evenly over its next hops (default: evenly
                                  over the pair's shortest routes) */
+#define SDNR_LFA_LINK_ONLY 0x20u /* sdnr_lfa_tables: link-protecting alternates
+                                 only -- node protection is neither evaluated
+                                 nor reported, and no neighbour-pair scratch
+                                 is needed */
 
 #define SDNR_UNREACHED (-1)
 #define SDNR_DIST_INF  0xFFFFu
@@ -491,6 +495,54 @@ int sdnr_failure_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *dst, int32_t nrow
                                  const uint64_t *weight, int32_t nscen, const int64_t *scen_off,
                                  const int32_t *scen_edges, double *load, double *lost,
                                  uint8_t *routed, uint32_t flags);
+
+/* Loop-free alternate (fast-reroute) backup next hops per destination: the
+ * neighbour a switch may hand a destination's traffic to the moment its
+ * primary link dies, without the packet coming back (RFC 5286; an OpenFlow
+ * fast-failover group's second bucket).  Integer and bit-exact.
+ *   pcost_all  [V][V] u32, row v = sdnr_cost_tables' pcost row of destination
+ *              v under the costs in force: P[d][x] = least cost x -> d,
+ *              SDNR_COST_INF: no route.  With no costs uploaded every link
+ *              costs 1 and the rows are hop counts;
+ *   dst        [ndst] destinations (dense ids); row i of the outputs is dst[i];
+ *   backup, backup_port [ndst][V] int32, kind [ndst][V] u8: WRITTEN;
+ *   counts     [ndst][4] u32 or NULL: WRITTEN -- the row's primaries, backups,
+ *              node-protecting backups and downstream backups.
+ * The primary of (s, d) is p = the smallest out-neighbour of s with
+ * cost(s -> p) + P[d][p] == P[d][s] (sdnr_cost_tables' nh); there is none at
+ * s == d or where P[d][s] is SDNR_COST_INF.  A candidate is an out-link
+ * e = (s -> n) with n != p and P[d][n] finite.  It is
+ *   loop-free (link-protecting) iff P[s][n] is INF or P[d][n] < P[s][n] + P[d][s]
+ *              (no least-cost route n -> d visits s),
+ *   downstream iff P[d][n] < P[d][s],
+ *   node-protecting iff loop-free and (P[p][n] is INF or
+ *              P[d][n] < P[p][n] + P[d][p]) (no least-cost route n -> d visits
+ *              p; never when p == d).
+ * The backup is the loop-free candidate of the smallest key (not
+ * node-protecting, cost[e] + P[d][n], n); with SDNR_LFA_LINK_ONLY the key is
+ * (cost[e] + P[d][n], n).  backup = that n, backup_port = that link's port,
+ * kind = 1 | downstream << 1 | node-protecting << 2; -1 / -1 / 0 where there is
+ * no primary or no backup.  The sums are taken in 64 bits (two table entries
+ * may reach 2^32) and INF enters none.
+ * A pre-pass gathers P[s][n] per link and, unless SDNR_LFA_LINK_ONLY is set,
+ * P[n_j][n_i] per pair of neighbours of a vertex (the sum of the squared
+ * out-degrees, 4 bytes each) into the context scratch: more than 1 GiB of them
+ * is SDNR_ERR_NOMEM (use SDNR_LFA_LINK_ONLY).  V is at most 16,384
+ * (sdnr_apsp's cap: a 1 GiB table, a 64 KiB row in LDS), above it
+ * SDNR_ERR_INVAL before anything is read: the fat-tree k=48 and the dragonfly
+ * fit, the torus 32^3 and the 100k Jellyfish cannot hold an all-pairs table
+ * and are out of scope.
+ * Device pointers only (flags must hold SDNR_DEVICE_PTRS); asynchronous on the
+ * context stream; on a multi-device context it runs on the primary device;
+ * SDNR_TIMING times the main kernel (not the pre-pass).  Without an uploaded
+ * graph: SDNR_ERR_STATE.  ndst == 0: SDNR_OK, nothing touched.  A dst[i]
+ * outside [0, V) is an empty row (-1 / -1 / 0, counts 0).  A requested row
+ * with P[d][d] != 0, or with a vertex of finite cost > 0 that has no tight
+ * link (such a vertex gets no primary), is reported by sdnr_synchronize as
+ * SDNR_ERR_INVAL; the other rows of the call are unaffected. */
+int sdnr_lfa_tables(sdnr_ctx *ctx, const uint32_t *pcost_all, const int32_t *dst, int32_t ndst,
+                    int32_t *backup, int32_t *backup_port, uint8_t *kind, uint32_t *counts,
+                    uint32_t flags);
 
 /* Flood ports (TopologyManager._is_edge_port / _do_broadcast, reference
  * sdnmpi/topology.py:150-177): is_edge[i] = 1 iff ports[i] is neither end of

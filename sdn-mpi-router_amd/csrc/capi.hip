@@ -73,6 +73,11 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "outside [0, E) (ignored), a scenario list that is not ascending, "
                              "pair_off or scen_off outside their lists, relaxation sweeps that "
                              "outran V or a route count above the double range: loads invalid");
+        if (h & kErrLfa)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_lfa_tables: a requested row of pcost_all is "
+                             "not a least-cost labelling of the uploaded graph under the costs in "
+                             "force (P[d][d] != 0, or a vertex of finite cost > 0 without a tight "
+                             "link): that row invalid");
         if (h & kErrCostTables)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_tables: V relaxation sweeps did not reach "
                              "the fixed point (link costs outside what sdnr_graph_costs accepts): "
@@ -574,11 +579,13 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
         return sdnr_fail(SDNR_ERR_INVAL, "graph_upload: row_ptr[0]=%d row_ptr[V]=%d, E=%d",
                          row_ptr[0], row_ptr[V], E);
     int32_t maxdeg = 0;
+    uint64_t deg2 = 0;
     bool port16 = true;
     for (int32_t u = 0; u < V; ++u) {
         const int32_t a = row_ptr[u], b = row_ptr[u + 1];
         if (b < a) return sdnr_fail(SDNR_ERR_INVAL, "graph_upload: row_ptr decreases at %d", u);
         if (b - a > maxdeg) maxdeg = b - a;
+        deg2 += (uint64_t)(b - a) * (uint64_t)(b - a);
         for (int32_t e = a; e < b; ++e) {
             if (port[e] < 0 || port[e] >= 0xFFFF) port16 = false;
             if (col[e] < 0 || col[e] >= V)
@@ -839,6 +846,7 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
     ctx->W = W;
     ctx->plane_depth = 0;
     ctx->max_deg = maxdeg;
+    ctx->deg2_sum = deg2;
     ctx->max_indeg = max_indeg;
     ctx->port16 = port16;
     ctx->symmetric = symmetric;
@@ -1435,6 +1443,27 @@ int sdnr_failure_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *dst, int32_t nrow
     return sdnr_launch_failure_ecmp_link_loads(ctx, dst, nrows, pair_off, lo, hi, srcs, weight,
                                                nscen, scen_off, flo, fhi, scen_edges, load, lost,
                                                routed, (flags & SDNR_LOADS_SPLIT_HOP) != 0);
+}
+
+int sdnr_lfa_tables(sdnr_ctx *ctx, const uint32_t *pcost_all, const int32_t *dst, int32_t ndst,
+                    int32_t *backup, int32_t *backup_port, uint8_t *kind, uint32_t *counts,
+                    uint32_t flags)
+{
+    CHECK_CTX(ctx);
+    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_lfa_tables: no graph uploaded");
+    if (!(flags & SDNR_DEVICE_PTRS))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_lfa_tables: device pointers only");
+    if (ndst < 0) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_lfa_tables: negative count");
+    if (ctx->V > kLfaMaxV)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_lfa_tables: V=%d above %d (the all-pairs table "
+                         "and its LDS row)", ctx->V, kLfaMaxV);
+    if (ndst == 0 || ctx->V == 0) return SDNR_OK;
+    if (!pcost_all || !dst || !backup || !backup_port || !kind)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_lfa_tables: null pointer");
+    SDNR_HIP(hipSetDevice(ctx->device));
+    ctx->timed = (flags & SDNR_TIMING) != 0;
+    return sdnr_launch_lfa_tables(ctx, pcost_all, dst, ndst, backup, backup_port, kind, counts,
+                                  (flags & SDNR_LFA_LINK_ONLY) != 0);
 }
 
 int sdnr_apsp(sdnr_ctx *ctx, uint16_t *dist, uint32_t flags)

@@ -50,6 +50,7 @@ struct sdnr_ctx {
 
     // graph (device)
     int32_t V = -1, E = 0, max_deg = 0;
+    uint64_t deg2_sum = 0;              // sum of squared out-degrees (sdnr_lfa_tables' nn entries)
     int32_t max_indeg = 0x7FFFFFFF;     // maximum in-degree (set with adj16/radj16)
     int32_t W = 0;                      // ELL row width (0: CSR only)
     int32_t *row_ptr = nullptr, *col = nullptr, *port = nullptr;
@@ -222,6 +223,13 @@ constexpr int kFailureBytesPerV = 23;
 constexpr int kFailureLdsMaxV = SDNR_LDS_PER_CU / kFailureBytesPerV / 100 * 100;
 static_assert(kFailureLdsMaxV == 7100 && kFailureLdsMaxV < 0xFFFF, "depths in LDS are u16");
 
+constexpr int kErrLfa = 131072; // sdnr_lfa_tables: a row with P[d][d] != 0 / a vertex of finite cost > 0 without a tight link
+
+// sdnr_lfa_tables reads an all-pairs [V][V] u32 table and keeps one row of it
+// in LDS (64 KiB at the cap, sdnr_apsp's); its per-link and per-neighbour-pair
+// pre-pass arrays live in the context scratch (at most kLoadsScratchBytes)
+constexpr int kLfaMaxV = 16384;
+
 // error plumbing (capi.hip)
 int sdnr_fail(int code, const char *fmt, ...);
 int sdnr_hip_fail(hipError_t e, const char *what);
@@ -312,5 +320,9 @@ int sdnr_launch_failure_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *d_dst, int
                                         int64_t scen_hi, const int32_t *d_scen_edges,
                                         double *d_load, double *d_lost, uint8_t *d_routed,
                                         bool hop);
+// loop-free alternate next hops per destination (lfa_tables.hip)
+int sdnr_launch_lfa_tables(sdnr_ctx *ctx, const uint32_t *d_pcost_all, const int32_t *d_dst,
+                           int32_t ndst, int32_t *d_backup, int32_t *d_backup_port,
+                           uint8_t *d_kind, uint32_t *d_counts, bool link_only);
 int sdnr_launch_edge_ports(sdnr_ctx *ctx, const uint64_t *d_ends, int32_t nends,
                            const uint64_t *d_ports, int32_t nports, uint8_t *d_is_edge);

@@ -27,6 +27,7 @@ TIMING = 0x2
 SAME_TABLES = 0x4        # route expansion: the previous call's parent / port tables
 LOADS_TO_ROOT = 0x8      # sdnr_link_loads: per-destination next-hop rows
 LOADS_SPLIT_HOP = 0x10   # sdnr_ecmp_link_loads: even split over a switch's next hops
+LFA_LINK_ONLY = 0x20     # sdnr_lfa_tables: link-protecting alternates only
 UNREACHED = -1
 DIST_INF = 0xFFFF
 TREE_NONE = 0xFFFFFFFF
@@ -48,7 +49,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_edge_ports", "sdnr_dfs_rows_affected", "sdnr_link_loads",
     "sdnr_ecmp_link_loads", "sdnr_graph_costs", "sdnr_cost_tables",
     "sdnr_cost_ecmp_link_loads", "sdnr_graph_twin_reps", "sdnr_last_dfs_searched",
-    "sdnr_failure_ecmp_link_loads",
+    "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables",
 )
 
 
@@ -111,6 +112,7 @@ def _bind(L):
         "sdnr_cost_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, vp, u32], c_int),
         "sdnr_failure_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, u32],
                                          c_int),
+        "sdnr_lfa_tables": ([vp, vp, vp, i32, vp, vp, vp, vp, u32], c_int),
         "sdnr_graph_twin_reps": ([vp, vp], c_int),
         "sdnr_last_dfs_searched": ([vp, ctypes.POINTER(i32)], c_int),
     }
@@ -518,6 +520,22 @@ class Context(object):
             self._h, p(dst_ptr), int(nrows), p(pair_off_ptr), p(srcs_ptr), p(weight_ptr),
             int(nscen), p(scen_off_ptr), p(scen_edges_ptr), p(load_ptr), p(lost_ptr),
             p(routed_ptr), flags))
+
+    def lfa_tables_device(self, pcost_all_ptr, dst_ptr, ndst, backup_ptr, backup_port_ptr,
+                          kind_ptr, counts_ptr=0, link_only=False, timing=False):
+        """Loop-free alternate next hops of ``ndst`` destinations
+        (sdnr_lfa_tables, device pointers, asynchronous): ``pcost_all`` u32
+        [V][V], row v = the least costs toward v under the costs in force (none
+        uploaded: every link costs 1); written: ``backup``, ``backup_port``
+        int32 [ndst][V], ``kind`` u8 [ndst][V] (1 = a backup exists, 2 =
+        downstream, 4 = node-protecting) and, unless 0, ``counts`` u32
+        [ndst][4] (primaries, backups, node-protecting, downstream).
+        ``link_only``: SDNR_LFA_LINK_ONLY."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0) | (LFA_LINK_ONLY if link_only else 0)
+        p = lambda a: ctypes.c_void_p(a) if a else None    # noqa: E731
+        _check(self._lib.sdnr_lfa_tables(
+            self._h, p(pcost_all_ptr), p(dst_ptr), int(ndst), p(backup_ptr), p(backup_port_ptr),
+            p(kind_ptr), p(counts_ptr), flags))
 
     def apsp(self):
         dist = np.empty((self.V, self.V), np.uint16)

@@ -45,7 +45,8 @@ __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "check_link_costs", "COST_INF", "COST_MAX", "COST_LDS_MAX_V", "COST_LDS_B8_MAX_V",
            "cost_ecmp_link_loads_host", "least_cost_paths_lex", "count_least_cost_paths",
            "COST_ECMP_LDS_MAX_V", "FAILURE_LDS_MAX_V", "normalise_scenarios",
-           "failure_ecmp_link_loads_host"]
+           "failure_ecmp_link_loads_host", "lfa_tables_host", "LFA_MAX_V", "LFA_BACKUP",
+           "LFA_DOWNSTREAM", "LFA_NODE"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -631,6 +632,96 @@ def failure_ecmp_link_loads_host(csr, cost, dsts, rows, srcs, weights=None, scen
     return load, lost, routed
 
 
+LFA_MAX_V = 16384               # csrc/common.h kLfaMaxV: sdnr_lfa_tables' cap (sdnr_apsp's)
+LFA_BACKUP, LFA_DOWNSTREAM, LFA_NODE = 1, 2, 4     # bits of sdnr_lfa_tables' kind
+
+
+def lfa_tables_host(csr, cost, pcost_all, dsts, link_only=False):
+    """numpy restatement of sdnr_lfa_tables (the CPU tests' engine double and
+    the checker of lfa_tables.hip): (backup int32 [D, V], backup_port int32,
+    kind uint8, counts uint32 [D, 4]) -- the loop-free alternate next hop of
+    every switch toward each destination of ``dsts``.
+
+    ``pcost_all``: [V, V] u32 (or int32 holding u32), row v = the least costs
+    toward v under ``cost`` (uint32 [E]; None: every link costs 1).  For the
+    primary p of (s, d) -- the first tight link of s's row; none at s == d or
+    where there is no route -- a neighbour n != p of finite P[d][n] is
+    loop-free iff P[s][n] is INF or P[d][n] < P[s][n] + P[d][s], downstream iff
+    P[d][n] < P[d][s], node-protecting iff loop-free and (P[p][n] is INF or
+    P[d][n] < P[p][n] + P[d][p]); the backup is the loop-free one of the
+    smallest (not node-protecting, cost + P[d][n], n) -- (cost + P[d][n], n)
+    with ``link_only``, which never reports node protection.  ``kind``:
+    LFA_BACKUP | LFA_DOWNSTREAM | LFA_NODE bits; ``counts``: primaries,
+    backups, node-protecting and downstream backups of each row.
+
+    Deliberately not the kernel's shape: per destination row, masks over all E
+    links at once and one ``np.lexsort`` for the choice; of ``pcost_all`` only
+    the requested rows, P[s][n] per link and P[p][n] per loop-free candidate
+    are gathered.  Python ints / int64 throughout: no sum can wrap."""
+    V, E = int(csr.V), int(csr.E)
+    cost = np.ones(E, np.uint32) if cost is None else check_link_costs(csr, cost)
+    P = _pcost_u32(pcost_all)
+    if P.shape != (V, V):
+        raise ValueError("pcost_all is the [V, V] all-pairs table (row v: destination v)")
+    dsts = np.asarray(dsts, np.int64)
+    D = int(dsts.shape[0])
+    backup = np.full((D, V), -1, np.int32)
+    bport = np.full((D, V), -1, np.int32)
+    kind = np.zeros((D, V), np.uint8)
+    counts = np.zeros((D, 4), np.uint32)
+    if E == 0 or D == 0:
+        return backup, bport, kind, counts
+    rp = np.asarray(csr.row_ptr, np.int64)
+    col = np.asarray(csr.col, np.int64)
+    port = np.asarray(csr.port, np.int32)
+    esrc = np.repeat(np.arange(V, dtype=np.int64), np.diff(rp))
+    c64 = cost.astype(np.int64)
+    eid = np.arange(E, dtype=np.int64)
+    INF = int(COST_INF)
+    back = P[esrc, col].astype(np.int64)                    # P[s][n] of every link
+    for i, d in enumerate(dsts.tolist()):
+        if d < 0 or d >= V:
+            continue                                       # unknown destination: empty row
+        Pd = P[d].astype(np.int64)
+        Ps, Pn = Pd[esrc], Pd[col]
+        reach = (Pn != INF) & (Ps != INF) & (esrc != d)
+        # the primary: the first tight link of each row
+        te = np.nonzero(reach & (c64 + Pn == Ps))[0]
+        x, first = np.unique(esrc[te], return_index=True)
+        prim = np.full(V, -1, np.int64)
+        prim[x] = te[first]
+        pe = prim[esrc]
+        lf = reach & (pe >= 0) & (eid != pe)
+        lf &= (back == INF) | (Pn < back + Ps)
+        ce = np.nonzero(lf)[0]                              # the loop-free candidates
+        counts[i, 0] = x.shape[0]
+        if ce.size == 0:
+            continue
+        cs, cn = esrc[ce], col[ce]
+        if link_only:
+            npro = np.zeros(ce.shape[0], bool)
+        else:
+            p = col[pe[ce]]
+            ppn = P[p, cn].astype(np.int64)                 # P[p][n]
+            npro = (ppn == INF) | (Pn[ce] < ppn + Pd[p])
+        order = np.lexsort((cn, c64[ce] + Pn[ce], ~npro, cs))
+        s_sorted = cs[order]
+        head = np.ones(order.shape[0], bool)
+        head[1:] = s_sorted[1:] != s_sorted[:-1]
+        win = order[head]
+        ws, we = cs[win], ce[win]
+        backup[i, ws] = col[we]
+        bport[i, ws] = port[we]
+        k = np.full(win.shape[0], LFA_BACKUP, np.uint8)
+        k[Pn[we] < Ps[we]] |= LFA_DOWNSTREAM
+        k[npro[win]] |= LFA_NODE
+        kind[i, ws] = k
+        counts[i, 1] = win.shape[0]
+        counts[i, 2] = int(npro[win].sum())
+        counts[i, 3] = int((Pn[we] < Ps[we]).sum())
+    return backup, bport, kind, counts
+
+
 class RouteEngine(object):
     """The GPU route engine of one TopologyDB: HIP device ``device`` (int),
     or the devices of a list (single-process multi-GPU, sources sharded over
@@ -1123,6 +1214,50 @@ class RouteEngine(object):
         else:
             routed[:, order] = got
         return load, d_lost.cpu().numpy(), routed
+
+    def lfa_tables(self, export, cost, pcost_all, dsts, link_only=False, timing=False):
+        """Loop-free alternate next hops (lfa_tables.hip, sdnr_lfa_tables):
+        (backup, backup_port int32 [D, V], kind uint8 [D, V] on the device,
+        counts uint32 [D, 4] on the host) for the destinations ``dsts``, as
+        ``lfa_tables_host`` defines them.
+
+        ``cost``: uint32 [E] link costs, or None for unit costs (the context's
+        costs are then cleared); ``pcost_all``: the [V, V] all-pairs least-cost
+        table under those costs, row v = destination v -- a device tensor
+        (int32 holding u32, as ``cost_tables`` returns it) or a numpy array,
+        which is uploaded.  ``link_only``: SDNR_LFA_LINK_ONLY.  A destination
+        outside [0, V) gives an empty row.  V above ``LFA_MAX_V`` raises."""
+        if cost is None:
+            self.load(export)
+            if self._costs is not None:
+                self._costs = None
+                self.ctx.set_link_costs(None)
+        else:
+            self.set_link_costs(export, cost)
+        t = self._torch
+        V = int(export.csr.V)
+        d = np.asarray(dsts, np.int64)
+        D = int(d.shape[0])
+        d = np.where((d < 0) | (d >= V), -1, d).astype(np.int32)
+        if _is_np(pcost_all):
+            pcost_all = t.from_numpy(np.ascontiguousarray(_pcost_u32(pcost_all)).view(np.int32)
+                                     ).to(self.dev)
+        if tuple(pcost_all.shape) != (V, V) or pcost_all.element_size() != 4:
+            raise ValueError("pcost_all is the [V, V] 4-byte all-pairs table (row v: "
+                             "destination v)")
+        pcost_all = pcost_all.contiguous()
+        backup = self._empty(D, V, t.int32)
+        bport = self._empty(D, V, t.int32)
+        kind = self._empty(D, V, t.uint8)
+        counts = t.zeros((D, 4), dtype=t.int32, device=self.dev)
+        if D and V:
+            td = t.from_numpy(d).to(self.dev)
+            self._ready()
+            self.ctx.lfa_tables_device(pcost_all.data_ptr(), td.data_ptr(), D, backup.data_ptr(),
+                                       bport.data_ptr(), kind.data_ptr(), counts.data_ptr(),
+                                       link_only=link_only, timing=timing)
+            self.ctx.synchronize()          # raises on a row that is no least-cost labelling
+        return backup, bport, kind, counts.cpu().numpy().view(np.uint32)
 
     def edge_ports(self, ends, ports):
         """Flood-port mask (sdnr_edge_ports, reference topology.py:150-155):

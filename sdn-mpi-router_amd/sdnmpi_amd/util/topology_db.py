@@ -26,7 +26,7 @@ first route query raises (``sdnmpi_amd._native.NativeUnavailable`` /
 
 import numpy as np
 
-from ..engine import (COST_MAX, DEFAULT_TABLE_BUDGET, INT32, RouteEngine, TableCache, _gather,
+from ..engine import (COST_MAX, DEFAULT_TABLE_BUDGET, INT32, LFA_MAX_V, RouteEngine, TableCache, _gather,
                       _host, _take, _torch, _u16, check_link_costs, least_cost_paths_lex,
                       shortest_paths_lex, tree_path)
 from ..graph import TrackedDict, Versions, export_graph, update_export
@@ -1087,6 +1087,115 @@ class TopologyDB(object):
                                                   (host[0][k].view(np.int32), host[1][k],
                                                    host[2][k]))
         return out
+
+    # -- loop-free alternates (fast reroute) -------------------------------
+    def _lfa_rows(self, ex, node_protect=True):
+        """(backup, backup_port, kind [V, V] tables as the engine returned
+        them, row d = destination d; counts uint32 [V, 4] on the host) of every
+        destination, kept in the least-cost memo: dropped with it when the
+        export or the costs change."""
+        V = int(ex.csr.V)
+        if V > LFA_MAX_V:
+            raise ValueError("loop-free alternates need the all-pairs least-cost table: %d "
+                             "switches are above the %d it is computed for" % (V, LFA_MAX_V))
+        if V > self._cost_cap(ex):
+            raise ValueError("loop-free alternates need the all-pairs least-cost table: %d x %d "
+                             "rows of 12 bytes per vertex do not fit the table budget" % (V, V))
+        m = self._cost_rows(ex, [])
+        if "pall" not in m:
+            # (pcost, nh) [V, V] with row d = destination d, out of the memo's slots
+            m = self._cost_rows(ex, list(range(V)))
+            idx = np.asarray([m["slot"][v] for v in range(V)], np.int64)
+            same = len(m["slot"]) == V and np.array_equal(idx, np.arange(V))
+            m["pall"] = tuple(t if same else _take(t, idx) for t in m["tabs"][:2])
+        lfa = m.setdefault("lfa", {})
+        key = bool(node_protect)
+        if key not in lfa:
+            lfa[key] = tuple(self.engine.lfa_tables(ex, self._cost_vector(ex), m["pall"][0],
+                                                    np.arange(V, dtype=np.int32),
+                                                    link_only=not key))
+        return lfa[key]
+
+    def lfa_tables(self, vertices=None, node_protect=True):
+        """Loop-free alternate (RFC 5286 fast-reroute) next hops under the link
+        costs (lfa_tables.hip) toward every host-bearing switch, or the dense
+        ``vertices`` given: dict(destinations, backup, backup_port int32
+        [n, V] -- -1 where a switch has no primary or no alternate toward that
+        destination --, kind uint8 [n, V] with bits 1 = an alternate exists, 2 =
+        it is downstream (strictly closer to the destination), 4 = it is
+        node-protecting (avoids the primary next hop too), dpids).  The primary
+        is ``least_cost_tables``' ``nh``.  ``node_protect=False``: the cheapest
+        link-protecting alternate, node protection not evaluated.  Needs the
+        all-pairs least-cost table (reused from the least-cost memo): a
+        ValueError above 16,384 switches or when it does not fit the table
+        budget."""
+        ex = self.graph()
+        hv = self._host_vertices(ex) if vertices is None else [int(v) for v in vertices]
+        b, bp, k, _ = self._lfa_rows(ex, node_protect)
+        idx = np.asarray(hv, np.int64)
+        return {"destinations": np.asarray(hv, np.int32), "backup": _host(_take(b, idx)),
+                "backup_port": _host(_take(bp, idx)), "kind": _host(_take(k, idx)),
+                "dpids": ex.csr.dpids}
+
+    def find_route_protected(self, src_mac, dst_mac):
+        """``find_route_least_cost``'s route with the fast-failover bucket of
+        every hop: a list of (dpid, out_port, backup_port, kind) -- the port
+        of the switch's loop-free alternate toward the destination switch and
+        its ``lfa_tables`` kind bits, or (None, 0) where it has none and at the
+        last hop (the host port).  [] where there is no route."""
+        return self.find_routes_protected([(src_mac, dst_mac)])[0]
+
+    def find_routes_protected(self, pairs):
+        """:meth:`find_route_protected` over many (src_mac, dst_mac) pairs."""
+        pairs = list(pairs)
+        routes = self.find_routes_least_cost(pairs)
+        if not any(routes):
+            return [[] for _ in routes]
+        ex = self.graph()
+        _, bp, k, _ = self._lfa_rows(ex)
+        want = sorted(set(ex.index[r[-1][0]] for r in routes if r))
+        idx = np.asarray(want, np.int64)
+        hbp, hk = _host(_take(bp, idx)), _host(_take(k, idx))
+        at = {d: i for i, d in enumerate(want)}
+        out = []
+        for r in routes:
+            hops = []
+            if r:
+                row = at[ex.index[r[-1][0]]]
+                for dpid, op in r[:-1]:
+                    s = ex.index[dpid]
+                    kd = int(hk[row, s])
+                    hops.append((dpid, op, int(hbp[row, s]) if kd else None, kd))
+                hops.append((r[-1][0], r[-1][1], None, 0))
+            out.append(hops)
+        return out
+
+    def lfa_coverage(self, node_protect=True):
+        """How much of the fabric a fast-failover deployment protects, over
+        all destinations: dict(primaries -- the (switch, destination) pairs
+        that forward at all --, backups, node_protecting, downstream, and the
+        fractions coverage = backups / primaries, node_coverage,
+        downstream_coverage; 0.0 on a fabric without primaries)."""
+        ex = self.graph()
+        tot = self._lfa_rows(ex, node_protect)[3].astype(np.int64).sum(axis=0)
+        n = [int(x) for x in tot]
+        frac = (lambda a: float(a) / n[0] if n[0] else 0.0)
+        return {"primaries": n[0], "backups": n[1], "node_protecting": n[2], "downstream": n[3],
+                "coverage": frac(n[1]), "node_coverage": frac(n[2]),
+                "downstream_coverage": frac(n[3])}
+
+    def unprotected_links(self):
+        """{(src_dpid, dst_dpid): number of destinations whose primary next hop
+        is this link and has no loop-free alternate}, links with none omitted:
+        the cables a fast-failover deployment cannot cover."""
+        ex = self.graph()
+        V = int(ex.csr.V)
+        kind = _host(self._lfa_rows(ex)[2])
+        nh = _host(self._cost_memo["pall"][1])
+        dd, ss = np.nonzero((nh >= 0) & ((kind & 1) == 0))
+        keys, n = np.unique(ss.astype(np.int64) * V + nh[dd, ss], return_counts=True)
+        dpids = ex.csr.dpids
+        return {(int(dpids[q // V]), int(dpids[q % V])): int(c) for q, c in zip(keys, n)}
 
     def _switch_pair_cost_loads(self, ex, sv, dv, w):
         """(load uint64 [E], reach bool [n]) of switch pairs (dense ids sv ->
