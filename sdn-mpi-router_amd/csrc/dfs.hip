@@ -1706,9 +1706,12 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
     const int32_t *__restrict__ port, int W, const int32_t *__restrict__ ell_port,
     const int32_t *__restrict__ src, int nsrc, int32_t *__restrict__ out_parent,
     int32_t *__restrict__ out_port, int32_t *__restrict__ out_hops, int *__restrict__ err,
-    int flags)
+    int flags, const int32_t *__restrict__ live)
 {
     static_assert(NW >= 2, "wave 0 searches, the others decrement");
+    // the twin fold's live count (device memory: the host does not know it):
+    // only src[0 .. *live) is searched, no row is written behind it
+    if (live) nsrc = min(nsrc, *live);
     constexpr int U = 4;                         // init / flush vertices per thread per step
     constexpr int S = NW - 1;                    // workers
     constexpr int RING = 512;                    // children in flight (u16)
@@ -2731,17 +2734,10 @@ __global__ __launch_bounds__(256) void dfs_hops16_kernel(size_t n, const int32_t
         out[i] = (uint16_t)h[i];
 }
 
-// the strategy dispatch: one search per entry of d_src
-static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
-                        int32_t *d_parent, int32_t *d_port, int32_t *d_hops, uint32_t *d_tree,
-                        bool slots = false, bool hops16 = false)
+// the visited set and the stack of one search fit the LDS strategies
+static bool dfs_small(const sdnr_ctx *ctx, int nsrc)
 {
     const int V = ctx->V;
-    if (nsrc == 0 || V == 0) return SDNR_OK;
-    const bool packed = d_tree != nullptr;
-    const bool ell = ctx->W > 0;
-    const bool hops = d_hops != nullptr;
-    const bool narrow = ctx->max_deg <= SDNR_WAVE;     // one row = one wavefront
     const size_t small_b = dfs_lds_bytes_small(V);
     const size_t cu_blocks_small = SDNR_LDS_PER_CU / small_b;
     bool small = V < 65536 && small_b <= 64 * 1024 &&
@@ -2755,6 +2751,41 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
                  small_b <= SDNR_MAX_LDS_PER_BLOCK)
             small = true;
     }
+    return small;
+}
+
+// the counted-pop kernels apply; async: dfs_async_kernel is the strategy
+static bool dfs_count_ok(const sdnr_ctx *ctx, bool hops)
+{
+    return ctx->adj16 != nullptr && ctx->radj16 != nullptr && ctx->V < 65535 &&
+           dfs_lds_bytes_count(ctx->V, hops) <= SDNR_MAX_LDS_PER_BLOCK;
+}
+
+static bool dfs_async(const sdnr_ctx *ctx, int nsrc, bool hops)
+{
+    const char *force = getenv("SDNROUTE_DFS_STRATEGY");
+    return dfs_count_ok(ctx, hops) &&
+           dfs_lds_bytes_async(ctx->V, hops) <= SDNR_MAX_LDS_PER_BLOCK &&
+           (force ? !strcmp(force, "async") : dfs_small(ctx, nsrc));
+}
+
+// the strategy dispatch: one search per entry of d_src.  d_live (device, may
+// be null): only the first min(nsrc, *d_live) entries are searched and only
+// their rows written -- honoured where dfs_takes_live() says so, else every
+// entry is searched, so the caller pads the list with -1 (empty rows)
+static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
+                        int32_t *d_parent, int32_t *d_port, int32_t *d_hops, uint32_t *d_tree,
+                        bool slots = false, bool hops16 = false,
+                        const int32_t *d_live = nullptr)
+{
+    const int V = ctx->V;
+    if (nsrc == 0 || V == 0) return SDNR_OK;
+    const bool packed = d_tree != nullptr;
+    const bool ell = ctx->W > 0;
+    const bool hops = d_hops != nullptr;
+    const bool narrow = ctx->max_deg <= SDNR_WAVE;     // one row = one wavefront
+    const size_t small_b = dfs_lds_bytes_small(V);
+    const bool small = dfs_small(ctx, nsrc);
     size_t lds = small ? small_b : dfs_lds_bytes_global(V);
     if (lds > SDNR_MAX_LDS_PER_BLOCK)
         return sdnr_fail(SDNR_ERR_INVAL, "graph too large for the LDS visited set (V=%d)", V);
@@ -2796,10 +2827,8 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
         return SDNR_OK;
     }
 #endif
-    const bool count_ok = ctx->adj16 != nullptr && ctx->radj16 != nullptr && V < 65535 &&
-                          dfs_lds_bytes_count(V, hops) <= SDNR_MAX_LDS_PER_BLOCK;
-    const bool async_ok = count_ok && dfs_lds_bytes_async(V, hops) <= SDNR_MAX_LDS_PER_BLOCK;
-    const bool async = async_ok && (force ? !strcmp(force, "async") : small);
+    const bool count_ok = dfs_count_ok(ctx, hops);
+    const bool async = dfs_async(ctx, nsrc, hops);
     slots = slots && packed;
     const int hflags = hops && hops16 ? kFlagHops16 : 0;
     if (!async && !small && ell && ctx->W <= 32 && packed_ok() && split_ok() &&
@@ -2902,7 +2931,7 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
                            preswz ? rw : ctx->radj16, ctx->deg32, ctx->row_ptr,              \
                            ctx->port, ctx->W, ctx->ell_port, d_src, nsrc,                    \
                            P_ ? reinterpret_cast<int32_t *>(d_tree) : d_parent, d_port,      \
-                           d_hops, err, aflags);                                             \
+                           d_hops, err, aflags, d_live);                                     \
     } while (0)
 #define SDNR_ASYNC(N_, H_) SDNR_ASYNC_P(N_, H_, false)
         if (packed) {
@@ -3046,14 +3075,18 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
 // entry (all its out-neighbours are marked by the root's pop).  A batch
 // searches the first member of every class it holds (the leader) into a
 // scratch table set and derives every caller row from its leader's:
-//   prep    leaders, compacted to the front of a source list padded with -1
-//           (empty rows), and every position's leader row and leader
-//   search  the unchanged dispatch over that list
+//   prep    leaders, compacted to the front of a source list, their count,
+//           and every position's leader row and leader
+//   search  the unchanged dispatch over that list: dfs_async_kernel reads the
+//           count and searches the leaders only; for any other strategy the
+//           list is padded with -1 (empty rows)
 //   derive  row copy + the 2 + |row| patched entries, in the layout's encoding
 // ---------------------------------------------------------------------------
 constexpr int kFoldPrepThreads = 1024;
 constexpr int kFoldDeriveThreads = 256;
 constexpr int kFoldLdsMaxV = 8000;                       // two int tables of V entries in 64 KB
+constexpr int kFoldPrepListMax = 2 * kFoldPrepThreads;   // two positions per thread
+constexpr size_t kFoldLdsBytes = 64 * 1024 - 256;        // dynamic LDS of the prep kernel
 constexpr size_t kFoldScratchBytes = (size_t)1 << 30;    // above this the batch is not folded
 
 // one workgroup.  Two tables indexed by class (twin_rep): first = the lowest
@@ -3061,12 +3094,20 @@ constexpr size_t kFoldScratchBytes = (size_t)1 << 30;    // above this the batch
 // list; in LDS (lds != 0: V <= kFoldLdsMaxV, the whole table initialised
 // while the sources load) or in global memory (only the entries this batch
 // touches are initialised).  The leaders keep their batch order in csrc[0 ..
-// count), the rest of csrc is -1; lead[i] = leader row of position i (-1:
-// src[i] is no vertex), lsrc[i] = that leader's source
+// count), the rest of csrc is -1 when pad is set (else left as it is: the
+// search honours the count); lead[i] = leader row of position i (-1: src[i]
+// is no vertex), lsrc[i] = that leader's source
+//
+// lds == 2 (the tables and the list fit LDS, nsrc <= kFoldPrepListMax): every
+// thread keeps its two positions (2 tid, 2 tid + 1) and their classes in
+// registers from one load of src and rep, the sources also go to LDS, and the
+// compaction is one scan over both -- four LDS phases behind two dependent
+// global loads, where the general path below re-reads src and rep in every
+// phase and gathers lsrc from global memory
 __global__ __launch_bounds__(kFoldPrepThreads) void dfs_fold_prep_kernel(
-    int V, int nsrc, int lds, const int32_t *__restrict__ src, const int32_t *__restrict__ rep,
-    int32_t *gtab, int32_t *__restrict__ csrc, int32_t *__restrict__ lead,
-    int32_t *__restrict__ lsrc, int32_t *__restrict__ count)
+    int V, int nsrc, int lds, int pad, const int32_t *__restrict__ src,
+    const int32_t *__restrict__ rep, int32_t *gtab, int32_t *__restrict__ csrc,
+    int32_t *__restrict__ lead, int32_t *__restrict__ lsrc, int32_t *__restrict__ count)
 {
     constexpr int NWV = kFoldPrepThreads / SDNR_WAVE;
     constexpr int kNone = 0x7FFFFFFF;
@@ -3075,6 +3116,53 @@ __global__ __launch_bounds__(kFoldPrepThreads) void dfs_fold_prep_kernel(
     int32_t *first = lds ? fold_tab : gtab;
     int32_t *slot = first + V;
     const int tid = (int)threadIdx.x, lane = lane_id(), w = tid >> 6;
+    if (lds == 2) {
+        int32_t *ssrc = slot + V;                // the list, in LDS
+        const int i0 = 2 * tid, i1 = i0 + 1;
+        const int s0 = i0 < nsrc ? src[i0] : -1, s1 = i1 < nsrc ? src[i1] : -1;
+        const bool ok0 = s0 >= 0 && s0 < V, ok1 = s1 >= 0 && s1 < V;
+        const int r0 = ok0 ? rep[s0] : -1, r1 = ok1 ? rep[s1] : -1;
+        for (int v = tid; v < V; v += kFoldPrepThreads) first[v] = kNone;
+        if (i0 < nsrc) ssrc[i0] = s0;
+        if (i1 < nsrc) ssrc[i1] = s1;
+        __syncthreads();
+        if (ok0) atomicMin(&first[r0], i0);
+        if (ok1) atomicMin(&first[r1], i1);
+        __syncthreads();
+        const int f0 = ok0 ? first[r0] : -1, f1 = ok1 ? first[r1] : -1;
+        const bool l0 = ok0 && f0 == i0, l1 = ok1 && f1 == i1;
+        const uint64_t m0 = __ballot(l0), m1 = __ballot(l1);
+        if (lane == 0) wsum[w] = __popcll(m0) + __popcll(m1);
+        __syncthreads();
+        int off = 0, total = 0;
+        for (int k = 0; k < NWV; ++k) {
+            const int c = wsum[k];
+            if (k < w) off += c;
+            total += c;
+        }
+        const int p0 = off + lanes_below(m0) + lanes_below(m1), p1 = p0 + (l0 ? 1 : 0);
+        if (l0) {
+            csrc[p0] = s0;
+            slot[r0] = p0;
+        }
+        if (l1) {
+            csrc[p1] = s1;
+            slot[r1] = p1;
+        }
+        __syncthreads();
+        if (i0 < nsrc) {
+            lead[i0] = ok0 ? slot[r0] : -1;
+            lsrc[i0] = ok0 ? ssrc[f0] : -1;
+            if (pad && i0 >= total) csrc[i0] = -1;
+        }
+        if (i1 < nsrc) {
+            lead[i1] = ok1 ? slot[r1] : -1;
+            lsrc[i1] = ok1 ? ssrc[f1] : -1;
+            if (pad && i1 >= total) csrc[i1] = -1;
+        }
+        if (tid == 0) count[0] = total;
+        return;
+    }
     if (lds) {
         for (int v = tid; v < V; v += kFoldPrepThreads) first[v] = kNone;
     } else {
@@ -3125,7 +3213,7 @@ __global__ __launch_bounds__(kFoldPrepThreads) void dfs_fold_prep_kernel(
         }
         lead[i] = L;
         lsrc[i] = ls;
-        if (i >= base) csrc[i] = -1;
+        if (pad && i >= base) csrc[i] = -1;
     }
     if (tid == 0) count[0] = base;
 }
@@ -3256,6 +3344,20 @@ __global__ __launch_bounds__(kFoldDeriveThreads) void dfs_fold_derive_kernel(
     }
 }
 
+// the parts of the trimmed fold (A/B builds: -DSDNR_FOLD_PARTS=n leaves some
+// out): 1 the search honours the live count, 4 the prep kernel's short form
+#ifndef SDNR_FOLD_PARTS
+#define SDNR_FOLD_PARTS 5
+#endif
+
+// the dispatch honours a live count for this call: dfs_async_kernel, run
+// directly (the slot layout goes through int32 tables and a pack pass over
+// every row, which then must all be defined)
+static bool dfs_takes_live(const sdnr_ctx *ctx, int nsrc, bool hops, bool packed, bool slots)
+{
+    return dfs_async(ctx, nsrc, hops) && !(packed && slots);
+}
+
 // fold this batch?  Only a graph with twins, and by default only above 2.5
 // sources per CU, the measured crossover at k=48 (forced on,
 // 144 / 288 / 516 / 576 sources lose 6.6 / 0.8 / 0.6 us or tie, 720 / 864 /
@@ -3308,15 +3410,23 @@ int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
     // SDNROUTE_DFS_FOLD_LDS=0 keeps the class tables in global memory (tests)
     const char *fl = getenv("SDNROUTE_DFS_FOLD_LDS");
     const bool lds = V <= kFoldLdsMaxV && !(fl && !strcmp(fl, "0"));
+    // the prep kernel's short form: the tables and the list in LDS
+    const bool lds2 = lds && (SDNR_FOLD_PARTS & 4) && nsrc <= kFoldPrepListMax &&
+                      8 * (size_t)V + 4 * (size_t)nsrc <= kFoldLdsBytes;
+    // a strategy that honours the live count searches the leaders only; any
+    // other gets the list padded with -1, so that its rows stay defined
+    const bool live = (SDNR_FOLD_PARTS & 1) && dfs_takes_live(ctx, nsrc, hbytes != 0, packed, slots);
     const bool timed = ctx->timed;
     if (timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     hipLaunchKernelGGL(dfs_fold_prep_kernel, dim3(1), dim3(kFoldPrepThreads),
-                       lds ? 8 * (size_t)V : 0, ctx->stream, V, nsrc, lds ? 1 : 0, d_src,
+                       lds2 ? 8 * (size_t)V + 4 * (size_t)nsrc : (lds ? 8 * (size_t)V : 0),
+                       ctx->stream, V, nsrc, lds2 ? 2 : (lds ? 1 : 0), live ? 0 : 1, d_src,
                        ctx->twin_rep, tab, csrc, lead, lsrc, count);
     SDNR_HIP(hipGetLastError());
     ctx->timed = false;                          // the span is timed around the three launches
     rc = dfs_dispatch(ctx, csrc, nsrc, packed ? nullptr : t0, t1, th,
-                      packed ? reinterpret_cast<uint32_t *>(t0) : nullptr, slots, hops16);
+                      packed ? reinterpret_cast<uint32_t *>(t0) : nullptr, slots, hops16,
+                      live ? count : nullptr);
     ctx->timed = timed;
     if (rc) return rc;
     uint32_t *o0 = packed ? d_tree : reinterpret_cast<uint32_t *>(d_parent);
@@ -3326,10 +3436,10 @@ int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
     const int vec = (vec_ok(o0, 4 * (size_t)V) ? 1 : 0) |
                     (!packed && vec_ok(d_port, 4 * (size_t)V) ? 2 : 0) |
                     (hbytes && vec_ok(d_hops, (size_t)hbytes * V) ? 4 : 0);
+    const int fmt = packed ? (slots ? kTreeSlot : kTreePort16) : kTreeInt32;
     hipLaunchKernelGGL(dfs_fold_derive_kernel, dim3(nsrc), dim3(kFoldDeriveThreads), 0,
-                       ctx->stream, V, packed ? (slots ? kTreeSlot : kTreePort16) : kTreeInt32,
-                       hbytes, vec, d_src, lsrc, lead, ctx->row_ptr, ctx->col, ctx->port,
-                       reinterpret_cast<const uint32_t *>(t0), o0,
+                       ctx->stream, V, fmt, hbytes, vec, d_src, lsrc, lead, ctx->row_ptr,
+                       ctx->col, ctx->port, reinterpret_cast<const uint32_t *>(t0), o0,
                        reinterpret_cast<const uint32_t *>(t1), reinterpret_cast<uint32_t *>(d_port),
                        reinterpret_cast<const char *>(th), reinterpret_cast<char *>(d_hops));
     SDNR_HIP(hipGetLastError());

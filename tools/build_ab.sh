@@ -7,7 +7,9 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 C=$ROOT/sdn-mpi-router_amd/csrc
 OUT=$ROOT/tools/ab/$NAME; mkdir -p $OUT
 pids=()
-for f in capi dfs shortest apsp routes ecmp incremental; do
+# the product's own source list (sdnmpi_amd/_buildinfo.SOURCES), without the .hip
+SRCS=$(cd "$ROOT/sdn-mpi-router_amd" && python3 -c "from sdnmpi_amd import _buildinfo as B; print(' '.join(s[:-4] for s in B.SOURCES))")
+for f in $SRCS; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function "$@" -c -o $OUT/$f.o $C/$f.hip &
   pids+=($!)
 done
