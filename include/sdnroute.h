@@ -567,6 +567,12 @@ int sdnr_last_launches(const sdnr_ctx *ctx, int32_t *launches);
  * in the batch -- the other rows were derived (0 before the first call). */
 int sdnr_last_dfs_searched(sdnr_ctx *ctx, int32_t *n);
 
+/* Form of the search kernel in the last sdnr_dfs_tables* call: 0 the
+ * full-load form, 1 the low-load form -- a folded call whose previous call on
+ * this context (same graph upload, same batch size) left few live searches
+ * (does not wait; both forms compute the same tables). */
+int sdnr_last_dfs_form(const sdnr_ctx *ctx, int32_t *form);
+
 /* Bellman-Ford sweeps of the last sdnr_apsp call (the most any 8-row block
  * ran, summed over its relaxation launches; 0 with SDNROUTE_APSP_RELAX=0). */
 int sdnr_last_sweeps(const sdnr_ctx *ctx, int32_t *sweeps);

@@ -153,6 +153,8 @@ static void free_graph(sdnr_ctx *c)
     if (c->twin_rep) (void)hipFree(c->twin_rep);
     c->twin_rep = nullptr;
     c->has_twins = false;
+    ++c->upload_gen;                             // live counts of the old graph are no hint
+    memset(c->live_ring, 0, sizeof c->live_ring);
     if (c->radj16 && c->radj_owned) (void)hipFree(c->radj16);
     if (c->runs) (void)hipFree(c->runs);
     c->runs = nullptr;
@@ -303,6 +305,11 @@ int sdnr_create(int device, sdnr_ctx **out)
         e = hipHostMalloc(reinterpret_cast<void **>(&c->h_pub), 64,
                           hipHostMallocCoherent | hipHostMallocMapped);
     if (e == hipSuccess) memset(c->h_pub, 0, 64);
+    // words of its own for the fold's live count (h_pub[0..3] are the plane BFS's)
+    if (e == hipSuccess)
+        e = hipHostMalloc(reinterpret_cast<void **>(&c->h_live), 64,
+                          hipHostMallocCoherent | hipHostMallocMapped);
+    if (e == hipSuccess) memset(c->h_live, 0, 64);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&c->d_err), sizeof(int));
     if (e == hipSuccess) e = hipMemset(c->d_err, 0, sizeof(int));
     if (e != hipSuccess) {
@@ -376,6 +383,7 @@ int sdnr_destroy(sdnr_ctx *ctx)
     if (ctx->d_err) (void)hipFree(ctx->d_err);
     if (ctx->h_flag) (void)hipHostFree(ctx->h_flag);
     if (ctx->h_pub) (void)hipHostFree(ctx->h_pub);
+    if (ctx->h_live) (void)hipHostFree(ctx->h_live);
     if (ctx->ev_flag) (void)hipEventDestroy(ctx->ev_flag);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -1716,6 +1724,14 @@ int sdnr_last_dfs_searched(sdnr_ctx *ctx, int32_t *n)
     }
     SDNR_HIP(hipSetDevice(ctx->device));
     *n = sum;
+    return SDNR_OK;
+}
+
+int sdnr_last_dfs_form(const sdnr_ctx *ctx, int32_t *form)
+{
+    CHECK_CTX(ctx);
+    if (!form) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_last_dfs_form: null out");
+    *form = ctx->dfs_form;
     return SDNR_OK;
 }
 

@@ -42,6 +42,8 @@ __device__ __forceinline__ int lds_swz(int x) { return x ^ ((x >> 3) & 31); }
 
 // ------------------------------------------------------------------ host --
 
+constexpr int kLiveRing = 8;           // runs of folded launches whose published count is still told apart
+
 struct sdnr_ctx {
     int device = 0;
     int num_cus = 256;
@@ -99,6 +101,22 @@ struct sdnr_ctx {
     // folded (then the searched count is the int at the head of scratch3)
     int32_t dfs_nsrc = 0;
     bool dfs_folded = false;
+    int32_t dfs_form = 0;               // kDfsFormFull / kDfsFormLow of that launch's search
+    // the fold's live count as a hint for the next folded call (dfs.hip,
+    // DESIGN.md 4.1e): dfs_fold_derive_kernel stores sequence << 32 | count
+    // into h_live, a coherent mapped host word; the host reads it without
+    // waiting, and live_ring tells which launch a sequence number was: an
+    // entry is a run seq0..seq1 of consecutive folded launches of one upload
+    // and batch size (the host may be any number of equal calls ahead of the
+    // device).  Per context, so every peer and every stream's context has its own
+    unsigned long long *h_live = nullptr;
+    struct {
+        uint32_t seq0, seq1, gen;       // seq0 0: no launch
+        int32_t nsrc;
+    } live_ring[kLiveRing] = {};
+    int live_head = 0;                  // the newest run
+    uint32_t live_seq = 0;              // the last folded launch's sequence number
+    uint32_t upload_gen = 0;            // bumped by every graph upload (free_graph)
 
     // grow-only device scratch / staging
     void *scratch = nullptr;
@@ -173,6 +191,7 @@ inline const char *sdnr_tune_env(const char *name)
 #endif
 }
 
+constexpr int kDfsFormFull = 0, kDfsFormLow = 1;   // sdnr_ctx::dfs_form (sdnr_last_dfs_form)
 constexpr int kDictPad = 0x40000000;   // dictionary-row padding offset (u + pad >= V)
 constexpr int kDictMaxP = 255;         // pattern ids are bytes
 constexpr int kErrLastPort = 256;   // sdnr_route_expand_packed: a last port outside [0, 0xFFFF]

@@ -1734,6 +1734,12 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
 #ifndef SDNR_ASYNC_G_U16
 #define SDNR_ASYNC_G_U16 48
 #endif
+// the dword-paired rows at 4 waves: the folded search's low-load form only
+// (dfs_dispatch).  48 live searches of 1,152 sources, us per call at 8 / 16 /
+// 32 / 48: 86.3 / 72.4 / 64.1 / 64.4, the u16 rows 67.3
+#ifndef SDNR_ASYNC_G_DW4
+#define SDNR_ASYNC_G_DW4 32
+#endif
     // children per worker step: 16 (8 above 4 waves), and 16 with the
     // dword-paired rows of the 5-worker regime (8 loads): k=48 144 sources
     // 54.9 -> 48.8 us, one source 53.3 -> 47.2 us (fresher counts)
@@ -1745,7 +1751,8 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
     // 8, 214.1 at 32; gpurun_out/r5_abg5).  48 for the plain rows after a
     // second A/B on the final library (profiles/r05_async_g48_ab.log): 1,152
     // sources 79.5 -> 78.2 us, every smaller share within 0.3 us
-    constexpr int G = NW <= 4 ? (PAIR == 0 ? SDNR_ASYNC_G_U16 : SDNR_ASYNC_G)
+    constexpr int G = NW <= 4 ? (PAIR == 0 ? SDNR_ASYNC_G_U16
+                                           : (PAIR == 2 && NW == 4 ? SDNR_ASYNC_G_DW4 : SDNR_ASYNC_G))
                               : (PAIR == 2 ? SDNR_ASYNC_G_DW : (PAIR == 1 ? SDNR_ASYNC_G_P1 : 8));
     constexpr unsigned kSpin = 1u << 22;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -2769,6 +2776,13 @@ static bool dfs_async(const sdnr_ctx *ctx, int nsrc, bool hops)
            (force ? !strcmp(force, "async") : dfs_small(ctx, nsrc));
 }
 
+// what the low-load form of the folded 4-wave search changes (A/B builds:
+// -DSDNR_FOLD_LOW_FORM=n): 1 the speculative pop compiled out, 2 the
+// dword-paired worker rows (their step width: SDNR_ASYNC_G_DW4)
+#ifndef SDNR_FOLD_LOW_FORM
+#define SDNR_FOLD_LOW_FORM 2
+#endif
+
 // the strategy dispatch: one search per entry of d_src.  d_live (device, may
 // be null): only the first min(nsrc, *d_live) entries are searched and only
 // their rows written -- honoured where dfs_takes_live() says so, else every
@@ -2776,7 +2790,7 @@ static bool dfs_async(const sdnr_ctx *ctx, int nsrc, bool hops)
 static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
                         int32_t *d_parent, int32_t *d_port, int32_t *d_hops, uint32_t *d_tree,
                         bool slots = false, bool hops16 = false,
-                        const int32_t *d_live = nullptr)
+                        const int32_t *d_live = nullptr, bool low = false)
 {
     const int V = ctx->V;
     if (nsrc == 0 || V == 0) return SDNR_OK;
@@ -2901,7 +2915,7 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
         // (see dfs_async_kernel's SPEC; gpurun_out/r5_abr4, r5_abspec)
         bool specpop = true;
         if (const char *f = getenv("SDNROUTE_DFS_SPECPOP")) specpop = !strcmp(f, "1");
-        const bool spec = specpop;
+        bool spec = specpop;
         const int aflags = dfs_flags(kFlagPrio) | (preswz ? kFlagPreSwz : 0) | hflags |
                            (specpop ? kFlagSpecPop : 0);
         // paired worker rows (in-degree <= 32, pre-swizzled rows only);
@@ -2913,6 +2927,14 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
         const char *dq = sdnr_tune_env("SDNROUTE_DFS_DW");
         bool dw = preswz && !pair && !c16 && nw >= 6;
         if (dq) dw = preswz && !pair && !c16 && !strcmp(dq, "1");
+        // the folded search's low-load form (sdnr_launch_dfs asks for it when
+        // few searches are live): nw, the grid and the name stay the caller's
+        // nsrc's, only the instantiation differs, and both are bit-exact
+        if (low && d_live && !c16 && !pair) {
+            if (SDNR_FOLD_LOW_FORM & 1) spec = false;
+            if (SDNR_FOLD_LOW_FORM & 2) dw = preswz;
+            ctx->dfs_form = kDfsFormLow;
+        }
         int cgrid = (int)((size_t)ctx->num_cus * cpc);
         if (cgrid > nsrc) cgrid = nsrc;
         // the search wave issues at raised priority over the decrement
@@ -3280,12 +3302,21 @@ __global__ __launch_bounds__(kFoldDeriveThreads) void dfs_fold_derive_kernel(
     const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
     const int32_t *__restrict__ port, const uint32_t *__restrict__ in0,
     uint32_t *__restrict__ out0, const uint32_t *__restrict__ in1, uint32_t *__restrict__ out1,
-    const char *__restrict__ inh, char *__restrict__ outh)
+    const char *__restrict__ inh, char *__restrict__ outh, const int32_t *__restrict__ count,
+    unsigned long long *pub, uint32_t seq)
 {
     constexpr int kLast = kFoldDeriveThreads - SDNR_WAVE;    // first thread of the last wave
     const size_t i = blockIdx.x;
     const int tid = (int)threadIdx.x;
+    // pub (a coherent host word, may be null): the live count of this call
+    // for the host's choice of the next call's search form, one 8-byte store
+    // by one thread; its acknowledgement is waited for under the copy
+    const bool tell = pub && i == 0 && tid == 0;
+    const uint32_t searched = tell ? (uint32_t)count[0] : 0u;
     const int L = uniform(lead[i]), s = uniform(src[i]), ls = uniform(lsrc[i]);
+    if (tell)
+        __hip_atomic_store(pub, (unsigned long long)seq << 32 | searched, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
     const bool patch = L >= 0 && s != ls;        // else an empty row, or the leader's as it is
     const size_t ob = i * (size_t)V, lb = (size_t)(L < 0 ? 0 : L) * (size_t)V;
     int a = 0, d = 0;
@@ -3374,6 +3405,38 @@ static bool dfs_fold(const sdnr_ctx *ctx, int nsrc)
     return 2 * (int64_t)nsrc > 5 * (int64_t)ctx->num_cus;
 }
 
+// live searches per CU up to which the folded search takes its low-load form:
+// the boundary dfs_async_waves uses.  No crossover was found above it -- k=48,
+// 1,152 sources of which 48 / 256 / 512 / 1,152 are classes of their own, us
+// per call (median), full form 67.4 / 133.2 / 138.4 / 171.0, low form 62.9 /
+// 103.3 / 108.9 / 152.6 -- so above 2 per CU the full form
+// stays for what it is everywhere else, the choice of the unfolded path at
+// this load, until that path's own rows are measured again
+constexpr int kFoldLowPerCu = 2;
+
+// the folded search in its low-load form?  SDNROUTE_DFS_FOLD_FORM=full|low
+// forces either (A/B, tests)
+static bool dfs_fold_low(sdnr_ctx *ctx, int nsrc)
+{
+    if (const char *f = getenv("SDNROUTE_DFS_FOLD_FORM")) {
+        if (!strcmp(f, "full")) return false;
+        if (!strcmp(f, "low")) return true;
+    }
+    // the count the derive kernel of an earlier folded call published: read
+    // once, never waited for.  It counts only when its sequence number is a
+    // launch of this graph upload with this nsrc (live_ring); a stale or
+    // missing one only picks the slower of two bit-exact instantiations --
+    // the search itself reads the count from the device
+    const unsigned long long w = __atomic_load_n(ctx->h_live, __ATOMIC_RELAXED);
+    const uint32_t seq = (uint32_t)(w >> 32);
+    if (seq == 0) return false;
+    for (const auto &r : ctx->live_ring)
+        if (r.seq0 && seq - r.seq0 <= r.seq1 - r.seq0)       // the run that launch was in
+            return r.gen == ctx->upload_gen && r.nsrc == nsrc &&
+                   (int64_t)(uint32_t)w <= (int64_t)kFoldLowPerCu * ctx->num_cus;
+    return false;
+}
+
 int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
                     int32_t *d_parent, int32_t *d_port, int32_t *d_hops, uint32_t *d_tree,
                     bool slots, bool hops16)
@@ -3381,6 +3444,7 @@ int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
     const int V = ctx->V;
     ctx->dfs_nsrc = nsrc;
     ctx->dfs_folded = false;
+    ctx->dfs_form = kDfsFormFull;
     if (nsrc == 0 || V == 0 || !dfs_fold(ctx, nsrc))
         return dfs_dispatch(ctx, d_src, nsrc, d_parent, d_port, d_hops, d_tree, slots, hops16);
     const bool packed = d_tree != nullptr;
@@ -3416,6 +3480,21 @@ int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
     // a strategy that honours the live count searches the leaders only; any
     // other gets the list padded with -1, so that its rows stay defined
     const bool live = (SDNR_FOLD_PARTS & 1) && dfs_takes_live(ctx, nsrc, hbytes != 0, packed, slots);
+    const bool low = live && dfs_fold_low(ctx, nsrc);
+    uint32_t seq = 0;                            // this launch in the ring of published counts
+    if (live) {
+        if (!(seq = ++ctx->live_seq)) seq = ++ctx->live_seq;
+        auto *r = &ctx->live_ring[ctx->live_head];
+        if (r->seq0 && r->seq1 + 1 == seq && r->gen == ctx->upload_gen && r->nsrc == nsrc) {
+            r->seq1 = seq;                       // one more of the same run
+        } else {
+            ctx->live_head = (ctx->live_head + 1) % kLiveRing;
+            r = &ctx->live_ring[ctx->live_head];
+            r->seq0 = r->seq1 = seq;
+            r->gen = ctx->upload_gen;
+            r->nsrc = nsrc;
+        }
+    }
     const bool timed = ctx->timed;
     if (timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     hipLaunchKernelGGL(dfs_fold_prep_kernel, dim3(1), dim3(kFoldPrepThreads),
@@ -3426,7 +3505,7 @@ int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
     ctx->timed = false;                          // the span is timed around the three launches
     rc = dfs_dispatch(ctx, csrc, nsrc, packed ? nullptr : t0, t1, th,
                       packed ? reinterpret_cast<uint32_t *>(t0) : nullptr, slots, hops16,
-                      live ? count : nullptr);
+                      live ? count : nullptr, low);
     ctx->timed = timed;
     if (rc) return rc;
     uint32_t *o0 = packed ? d_tree : reinterpret_cast<uint32_t *>(d_parent);
@@ -3441,7 +3520,8 @@ int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
                        ctx->stream, V, fmt, hbytes, vec, d_src, lsrc, lead, ctx->row_ptr,
                        ctx->col, ctx->port, reinterpret_cast<const uint32_t *>(t0), o0,
                        reinterpret_cast<const uint32_t *>(t1), reinterpret_cast<uint32_t *>(d_port),
-                       reinterpret_cast<const char *>(th), reinterpret_cast<char *>(d_hops));
+                       reinterpret_cast<const char *>(th), reinterpret_cast<char *>(d_hops), count,
+                       live ? ctx->h_live : nullptr, seq);
     SDNR_HIP(hipGetLastError());
     ctx->dfs_folded = true;
     ctx->last_launches = 3;                      // prep, search, derive

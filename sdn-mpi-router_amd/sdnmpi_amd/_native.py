@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_edge_ports", "sdnr_dfs_rows_affected", "sdnr_link_loads",
     "sdnr_ecmp_link_loads", "sdnr_graph_costs", "sdnr_cost_tables",
     "sdnr_cost_ecmp_link_loads", "sdnr_graph_twin_reps", "sdnr_last_dfs_searched",
+    "sdnr_last_dfs_form",
     "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables",
 )
 
@@ -115,6 +116,7 @@ def _bind(L):
         "sdnr_lfa_tables": ([vp, vp, vp, i32, vp, vp, vp, vp, u32], c_int),
         "sdnr_graph_twin_reps": ([vp, vp], c_int),
         "sdnr_last_dfs_searched": ([vp, ctypes.POINTER(i32)], c_int),
+        "sdnr_last_dfs_form": ([vp, ctypes.POINTER(i32)], c_int),
     }
     # an A/B build named by SDNROUTE_LIB may predate some entry points: those
     # stay unbound (calling one raises AttributeError); the in-tree library
@@ -633,6 +635,14 @@ class Context(object):
         n = ctypes.c_int32()
         _check(self._lib.sdnr_last_dfs_searched(self._h, ctypes.byref(n)))
         return n.value
+
+    def last_dfs_form(self):
+        """"full" or "low": the form of the search kernel in the last DFS table
+        call (sdnr_last_dfs_form; low: a folded call after one that left few
+        live searches)."""
+        n = ctypes.c_int32()
+        _check(self._lib.sdnr_last_dfs_form(self._h, ctypes.byref(n)))
+        return "low" if n.value else "full"
 
     def last_sweeps(self):
         """Bellman-Ford sweeps of the last APSP call (sdnr_last_sweeps)."""

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """A/B of the k=48 packed DFS tables between library builds (diagnostic).
 
-    python tools/ab_lib_dfs.py [--fabric NAME] [--shortest] LIB[:ENV=VALUE] ...
+    python tools/ab_lib_dfs.py [--fabric NAME] [--shortest] [--live L,...] LIB[:ENV=VALUE] ...
 
 Each library is loaded through plain ctypes (no build-identity check, so an
 older build of the product library works too), the k=48 CSR uploaded, and
 sdnr_dfs_tables_packed timed with HIP events on 1, 144 and 1,152 host
 sources, libraries interleaved per repetition so box drift hits all alike.
+--live L,...: instead, lists of as many sources as the fabric has host-bearing
+switches, of which L are twin classes (a fat-tree: its edge switches are k
+classes, L - k of them are replaced by aggregation switches, classes of their
+own); n= in the output is then L, and the searched count is printed.
 """
 import ctypes
 import os
@@ -29,6 +33,7 @@ def open_lib(path):
     L.sdnr_shortest_tables.argtypes = [vp, vp, i32, vp, vp, vp, u32]
     L.sdnr_set_stream.argtypes = [vp, vp]
     L.sdnr_synchronize.argtypes = [vp]
+    L.sdnr_last_dfs_searched.argtypes = [vp, ctypes.POINTER(i32)]
     h = vp()
     assert L.sdnr_create(0, ctypes.byref(h)) == 0
     return L, h
@@ -43,6 +48,9 @@ def main():
     shortest = bool(args) and args[0] == "--shortest"
     if shortest:
         args = args[1:]
+    live = None
+    if args and args[0] == "--live":
+        live, args = [int(x) for x in args[1].split(",")], args[2:]
     specs = [(a.split(":", 1) + [""])[:2] for a in args]    # (library, "ENV=VALUE" or "")
     libs = [a for a in args]
     fabric = T.by_name(fab)
@@ -70,8 +78,20 @@ def main():
           if n <= len(srcs)]
     if only:
         ns = [n for n in ns if str(n) in only.split(",") or (n == len(srcs) and "all" in only)]
-    for n in sorted(set(ns)):
-        pick = srcs[np.linspace(0, len(srcs) - 1, n).astype(np.int64)]
+    lists = {n: srcs[np.linspace(0, len(srcs) - 1, n).astype(np.int64)] for n in set(ns)}
+    if live:
+        nb = np.unique(np.concatenate([col[rp[s]:rp[s + 1]] for s in srcs])).astype(np.int32)
+        nb = nb[~np.isin(nb, srcs)]              # a fat-tree's aggregation switches
+        pods = int(round((2 * len(srcs)) ** 0.5))            # k pods of k / 2 edge switches
+        lists = {}
+        for want in live:
+            n_agg = want - pods
+            assert 0 <= n_agg <= len(nb) and len(srcs) - n_agg >= pods, want
+            edges = srcs[np.linspace(0, len(srcs) - 1, len(srcs) - n_agg).astype(np.int64)]
+            lists[want] = np.concatenate([edges, nb[:n_agg]]).astype(np.int32)
+    for key in sorted(lists):
+        pick = lists[key]
+        n = len(pick)
         ts = torch.from_numpy(pick).to(dev)
         out = torch.empty((n, csr.V), dtype=torch.int32, device=dev)
         o2, o3 = torch.empty_like(out), torch.empty_like(out)
@@ -96,8 +116,12 @@ def main():
                 if k:
                     del os.environ[k]
                 if rep:
-                    res[p].setdefault(n, []).append(e0.elapsed_time(e1) / 10 * 1e3)
-        print("done n=%d" % n, file=sys.stderr, flush=True)      # progress (a silent run looks hung)
+                    res[p].setdefault(key, []).append(e0.elapsed_time(e1) / 10 * 1e3)
+        if live and not shortest:
+            got = ctypes.c_int32()
+            assert L.sdnr_last_dfs_searched(h, ctypes.byref(got)) == 0
+            print("live %d: %d sources, %d searched" % (key, n, got.value))
+        print("done n=%d" % key, file=sys.stderr, flush=True)    # progress (a silent run looks hung)
     for p in libs:
         print(fab, "shortest" if shortest else "dfs", os.path.basename(p), {n: round(float(np.median(v)), 1) for n, v in res[p].items()})
     for p in libs:                               # the spread: min / median / max, and every repetition
