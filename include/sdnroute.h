@@ -496,6 +496,65 @@ int sdnr_failure_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *dst, int32_t nrow
                                  const int32_t *scen_edges, double *load, double *lost,
                                  uint8_t *routed, uint32_t flags);
 
+/* Link-cost what-if: sdnr_cost_ecmp_link_loads once per COST scenario, without
+ * touching the uploaded graph, its costs or any table, and optionally the peak
+ * utilisation of every scenario.  A scenario is a set of cost overrides
+ * (directed link, new cost); the new cost SDNR_COST_INF takes the link down,
+ * so sdnr_failure_ecmp_link_loads is the special case of all-INF scenarios.
+ * The work per (scenario, destination row) is sdnr_failure_ecmp_link_loads',
+ * all of it in LDS, with the cost in force -- the base cost, the override, or
+ * down -- read at every step: the Bellman-Ford, the ordering of the least-cost
+ * DAG with its route counts, and the push.
+ *   dst, nrows, pair_off, srcs, weight, load, lost, routed: as in
+ *              sdnr_failure_ecmp_link_loads.  The call ADDS into load and lost;
+ *   scen_off   [nscen + 1] int64: the overrides of scenario k are entries
+ *              scen_off[k] .. scen_off[k+1] of scen_edges / scen_costs;
+ *   scen_edges CSR edge indices in [0, E), STRICTLY ascending within a scenario;
+ *   scen_costs parallel to scen_edges: the link's cost in this scenario, >= 1
+ *              with cost * (V - 1) < SDNR_COST_INF (sdnr_graph_costs' rule), or
+ *              SDNR_COST_INF: the link is down.  An override may lower a cost
+ *              as well as raise it.  (Both lists may be NULL when every
+ *              scenario is empty);
+ *   capacity   [E] double or NULL (1.0 per link), read only for peak;
+ *   peak       [nscen] double, WRITTEN: the max over e of load[k][e] /
+ *              capacity[e], over load as it stands after this call's additions
+ *              (0.0 when no link carries anything);
+ *   peak_edge  [nscen] int32, WRITTEN: the smallest e that attains peak[k], -1
+ *              when peak[k] is 0.  peak and peak_edge are both given or both
+ *              NULL.
+ * Defining property: slice k equals sdnr_cost_ecmp_link_loads over
+ * sdnr_cost_tables rows of a graph with the costs of scenario k really
+ * uploaded and its INF links really removed, scattered back to this graph's
+ * edge order; a link that is down carries exactly 0, also one that stays tight
+ * by its base cost.  The base cost of a link is the one sdnr_graph_costs
+ * uploaded, 1 when none was.  An empty scenario, and an override equal to the
+ * base cost, are the fabric as it is.  Overrides are directed.
+ * SDNR_LOADS_SPLIT_HOP, the sums (f64 atomics) and "no NaN or Inf reaches load
+ * or lost" as in sdnr_cost_ecmp_link_loads.  Device pointers only (flags must
+ * hold SDNR_DEVICE_PTRS); asynchronous on the context stream (the ends of
+ * pair_off and scen_off are read back first: not monotone is SDNR_ERR_INVAL);
+ * on a multi-device context it runs on the primary device; SDNR_TIMING times
+ * the main kernel (not the peak reduction), which sdnr_last_kernel names;
+ * sdnr_last_launches is 1.  Without an uploaded graph: SDNR_ERR_STATE.
+ * Negative counts, NULL where a buffer is required, one of peak / peak_edge
+ * without the other: SDNR_ERR_INVAL.  nscen == 0: SDNR_OK, nothing touched.
+ * nrows == 0 or no pairs: nothing is added; peak and peak_edge are still
+ * written from load as it stands.  A destination outside [0, V) is an empty
+ * row.  An override whose cost is 0 or breaks the cost rule, whose index is
+ * outside [0, E) or is not greater than its predecessor's is IGNORED -- the
+ * link keeps the cost it had -- and a capacity that is not finite or not > 0
+ * has its link left out of the peak; either, and offsets outside their lists,
+ * relaxation sweeps that outrun V or a route count above the double range, is
+ * reported by sdnr_synchronize as SDNR_ERR_INVAL.  The other scenarios of the
+ * call are unaffected and the context stays usable. */
+int sdnr_whatif_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *dst, int32_t nrows,
+                                const int64_t *pair_off, const int32_t *srcs,
+                                const uint64_t *weight, int32_t nscen, const int64_t *scen_off,
+                                const int32_t *scen_edges, const uint32_t *scen_costs,
+                                double *load, double *lost, uint8_t *routed,
+                                const double *capacity, double *peak, int32_t *peak_edge,
+                                uint32_t flags);
+
 /* Loop-free alternate (fast-reroute) backup next hops per destination: the
  * neighbour a switch may hand a destination's traffic to the moment its
  * primary link dies, without the packet coming back (RFC 5286; an OpenFlow

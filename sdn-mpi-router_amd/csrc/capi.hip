@@ -73,6 +73,13 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "outside [0, E) (ignored), a scenario list that is not ascending, "
                              "pair_off or scen_off outside their lists, relaxation sweeps that "
                              "outran V or a route count above the double range: loads invalid");
+        if (h & kErrWhatifLoads)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: a cost override that "
+                             "is 0, reaches SDNR_COST_INF times (V - 1), names an index outside "
+                             "[0, E) or does not ascend (ignored), a capacity that is not a "
+                             "positive finite number (that link skipped), pair_off or scen_off "
+                             "outside their lists, relaxation sweeps that outran V or a route "
+                             "count above the double range: loads invalid");
         if (h & kErrLfa)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_lfa_tables: a requested row of pcost_all is "
                              "not a least-cost labelling of the uploaded graph under the costs in "
@@ -1451,6 +1458,58 @@ int sdnr_failure_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *dst, int32_t nrow
     return sdnr_launch_failure_ecmp_link_loads(ctx, dst, nrows, pair_off, lo, hi, srcs, weight,
                                                nscen, scen_off, flo, fhi, scen_edges, load, lost,
                                                routed, (flags & SDNR_LOADS_SPLIT_HOP) != 0);
+}
+
+int sdnr_whatif_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *dst, int32_t nrows,
+                                const int64_t *pair_off, const int32_t *srcs,
+                                const uint64_t *weight, int32_t nscen, const int64_t *scen_off,
+                                const int32_t *scen_edges, const uint32_t *scen_costs,
+                                double *load, double *lost, uint8_t *routed,
+                                const double *capacity, double *peak, int32_t *peak_edge,
+                                uint32_t flags)
+{
+    CHECK_CTX(ctx);
+    if (ctx->V < 0)
+        return sdnr_fail(SDNR_ERR_STATE, "sdnr_whatif_ecmp_link_loads: no graph uploaded");
+    if (!(flags & SDNR_DEVICE_PTRS))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: device pointers only");
+    if (nrows < 0 || nscen < 0)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: negative count");
+    if ((peak == nullptr) != (peak_edge == nullptr))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: peak and peak_edge are "
+                         "both given or both NULL");
+    if (nscen == 0) return SDNR_OK;
+    if (!load || (nrows > 0 && (!dst || !pair_off || !scen_off)))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: null pointer");
+    SDNR_HIP(hipSetDevice(ctx->device));
+    if (nrows > 0) {
+        // the bounds of the pair list and of the override list
+        int64_t lo, hi, flo, fhi;
+        int rc = fetch_bounds(ctx, pair_off, nrows, &lo, &hi);
+        if (!rc) rc = fetch_bounds(ctx, scen_off, nscen, &flo, &fhi);
+        if (rc) return rc;
+        if (lo < 0 || hi < lo)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: pair_off not monotone "
+                             "(pair_off[0]=%lld, pair_off[%d]=%lld)", (long long)lo, nrows,
+                             (long long)hi);
+        if (flo < 0 || fhi < flo)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: scen_off not monotone "
+                             "(scen_off[0]=%lld, scen_off[%d]=%lld)", (long long)flo, nscen,
+                             (long long)fhi);
+        if (hi > lo && ctx->V > 0) {
+            if (!srcs || (fhi > flo && (!scen_edges || !scen_costs)))
+                return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: null pointer");
+            ctx->timed = (flags & SDNR_TIMING) != 0;
+            rc = sdnr_launch_whatif_ecmp_link_loads(ctx, dst, nrows, pair_off, lo, hi, srcs,
+                                                    weight, nscen, scen_off, flo, fhi, scen_edges,
+                                                    scen_costs, load, lost, routed,
+                                                    (flags & SDNR_LOADS_SPLIT_HOP) != 0);
+            if (rc) return rc;
+        }
+    }
+    // the reduction is over load as it stands now: the call ADDED into it
+    if (peak) return sdnr_launch_whatif_peak(ctx, nscen, load, capacity, peak, peak_edge);
+    return SDNR_OK;
 }
 
 int sdnr_lfa_tables(sdnr_ctx *ctx, const uint32_t *pcost_all, const int32_t *dst, int32_t ndst,

@@ -248,6 +248,7 @@ constexpr int kErrLfa = 131072; // sdnr_lfa_tables: a row with P[d][d] != 0 / a 
 // in LDS (64 KiB at the cap, sdnr_apsp's); its per-link and per-neighbour-pair
 // pre-pass arrays live in the context scratch (at most kLoadsScratchBytes)
 constexpr int kLfaMaxV = 16384;
+constexpr int kErrWhatifLoads = 262144; // sdnr_whatif_ecmp_link_loads: a bad override list / bad offsets / sweeps past V / a bad capacity
 
 // error plumbing (capi.hip)
 int sdnr_fail(int code, const char *fmt, ...);
@@ -339,6 +340,18 @@ int sdnr_launch_failure_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *d_dst, int
                                         int64_t scen_hi, const int32_t *d_scen_edges,
                                         double *d_load, double *d_lost, uint8_t *d_routed,
                                         bool hop);
+// ... once per cost scenario, the scenario's cost overrides in force (whatif_loads.hip),
+// and the peak utilisation of every [E] slice of a load plane
+int sdnr_launch_whatif_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *d_dst, int32_t nrows,
+                                       const int64_t *d_pair_off, int64_t pair_lo,
+                                       int64_t pair_hi, const int32_t *d_srcs,
+                                       const uint64_t *d_weight, int32_t nscen,
+                                       const int64_t *d_scen_off, int64_t scen_lo,
+                                       int64_t scen_hi, const int32_t *d_scen_edges,
+                                       const uint32_t *d_scen_costs, double *d_load,
+                                       double *d_lost, uint8_t *d_routed, bool hop);
+int sdnr_launch_whatif_peak(sdnr_ctx *ctx, int32_t nscen, const double *d_load,
+                            const double *d_capacity, double *d_peak, int32_t *d_peak_edge);
 // loop-free alternate next hops per destination (lfa_tables.hip)
 int sdnr_launch_lfa_tables(sdnr_ctx *ctx, const uint32_t *d_pcost_all, const int32_t *d_dst,
                            int32_t ndst, int32_t *d_backup, int32_t *d_backup_port,

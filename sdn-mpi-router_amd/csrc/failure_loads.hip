@@ -47,6 +47,7 @@
 // of the context scratch (the depths u32: 25 bytes per vertex), all of it read
 // and written with agent-scope relaxed accesses.
 #include "common.h"
+#include "rowstate.h"
 
 namespace {
 
@@ -55,56 +56,6 @@ namespace {
 constexpr int kFailThreads = 1024;
 constexpr uint32_t kFailInf = SDNR_COST_INF;
 constexpr int kNoFail = 0x7FFFFFFF;
-
-// row-state words: plain LDS accesses, or agent-scope relaxed ones on scratch
-// that other waves of the workgroup write
-template <bool LDS, typename T>
-__device__ __forceinline__ T fl_ld(const T *p)
-{
-    if (LDS) return *p;
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <bool LDS, typename T>
-__device__ __forceinline__ void fl_st(T *p, T v)
-{
-    if (LDS)
-        *p = v;
-    else
-        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <bool LDS>
-__device__ __forceinline__ double fl_ld_f64(const double *p)
-{
-    if (LDS) return *p;
-    // (also written by atomics performed in L2: read past L1)
-    return __longlong_as_double((long long)__hip_atomic_load(
-        reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED,
-        __HIP_MEMORY_SCOPE_AGENT));
-}
-
-template <bool LDS>
-__device__ __forceinline__ void fl_st_f64(double *p, double v)
-{
-    if (LDS)
-        *p = v;
-    else
-        __hip_atomic_store(reinterpret_cast<unsigned long long *>(p),
-                           (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <bool LDS>
-struct FailDepth {
-    typedef uint16_t T;
-    static constexpr int kPending = 0xFFFF;
-};
-template <>
-struct FailDepth<false> {
-    typedef uint32_t T;
-    static constexpr int kPending = 0x7FFFFFFF;
-};
 
 // The failed links of one scenario, fail[0 .. hi) ascending, seen from the row
 // walk of one vertex.  dead(e): is edge e failed -- e ascends along the walk,

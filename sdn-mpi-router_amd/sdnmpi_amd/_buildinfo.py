@@ -1,7 +1,7 @@
 """Build identity of libsdnroute.so.
 
 The library embeds a SHA-256 over the exact inputs it was compiled from --
-the product sources, the two headers and the compile flags -- and exports it
+the product sources, the headers and the compile flags -- and exports it
 as ``sdnr_build_id()`` (also as the byte marker ``SDNR_BUILD_ID:<hex>``, so a
 build script can read it without loading the library).  ``build()``
 recompiles whenever the tree's id differs from the library's, and the
@@ -21,8 +21,8 @@ INCLUDE = os.path.join(os.path.dirname(PKG), "include")
 # (losing variants live under tools/diag/)
 SOURCES = ("capi.hip", "dfs.hip", "shortest.hip", "apsp.hip", "routes.hip", "ecmp.hip",
            "incremental.hip", "loads.hip", "ecmp_loads.hip", "cost_tables.hip",
-           "cost_ecmp_loads.hip", "failure_loads.hip", "lfa_tables.hip")
-HEADERS = (("csrc", "common.h"), ("include", "sdnroute.h"))
+           "cost_ecmp_loads.hip", "failure_loads.hip", "lfa_tables.hip", "whatif_loads.hip")
+HEADERS = (("csrc", "common.h"), ("csrc", "rowstate.h"), ("include", "sdnroute.h"))
 FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function")
 MARKER = b"SDNR_BUILD_ID:"
 

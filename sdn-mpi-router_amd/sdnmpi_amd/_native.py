@@ -50,7 +50,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_ecmp_link_loads", "sdnr_graph_costs", "sdnr_cost_tables",
     "sdnr_cost_ecmp_link_loads", "sdnr_graph_twin_reps", "sdnr_last_dfs_searched",
     "sdnr_last_dfs_form",
-    "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables",
+    "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables", "sdnr_whatif_ecmp_link_loads",
 )
 
 
@@ -114,6 +114,8 @@ def _bind(L):
         "sdnr_failure_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, u32],
                                          c_int),
         "sdnr_lfa_tables": ([vp, vp, vp, i32, vp, vp, vp, vp, u32], c_int),
+        "sdnr_whatif_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp,
+                                         vp, vp, u32], c_int),
         "sdnr_graph_twin_reps": ([vp, vp], c_int),
         "sdnr_last_dfs_searched": ([vp, ctypes.POINTER(i32)], c_int),
         "sdnr_last_dfs_form": ([vp, ctypes.POINTER(i32)], c_int),
@@ -522,6 +524,27 @@ class Context(object):
             self._h, p(dst_ptr), int(nrows), p(pair_off_ptr), p(srcs_ptr), p(weight_ptr),
             int(nscen), p(scen_off_ptr), p(scen_edges_ptr), p(load_ptr), p(lost_ptr),
             p(routed_ptr), flags))
+
+    def whatif_ecmp_link_loads_device(self, dst_ptr, nrows, pair_off_ptr, srcs_ptr, weight_ptr,
+                                      nscen, scen_off_ptr, scen_edges_ptr, scen_costs_ptr,
+                                      load_ptr, lost_ptr=0, routed_ptr=0, capacity_ptr=0,
+                                      peak_ptr=0, peak_edge_ptr=0, hop=False, timing=False):
+        """Add the ECMP-over-least-cost link loads of a demand once per cost
+        scenario into ``load`` (f64 [nscen][E]; the caller zeroes it), the
+        scenario's overrides (CSR edge indices ``scen_edges[scen_off[k] ..
+        scen_off[k+1])``, strictly ascending, with the costs ``scen_costs``
+        beside them, COST_INF: the link is down) in force; ``lost`` and
+        ``routed`` as in ``failure_ecmp_link_loads_device``.  ``peak`` (f64
+        [nscen]) and ``peak_edge`` (int32 [nscen]), both or neither, are
+        written: the largest ``load[k][e] / capacity[e]`` (``capacity_ptr`` 0:
+        1.0 per link) and the first link that attains it:
+        sdnr_whatif_ecmp_link_loads, device pointers, asynchronous."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_SPLIT_HOP if hop else 0)
+        p = lambda a: ctypes.c_void_p(a) if a else None    # noqa: E731
+        _check(self._lib.sdnr_whatif_ecmp_link_loads(
+            self._h, p(dst_ptr), int(nrows), p(pair_off_ptr), p(srcs_ptr), p(weight_ptr),
+            int(nscen), p(scen_off_ptr), p(scen_edges_ptr), p(scen_costs_ptr), p(load_ptr),
+            p(lost_ptr), p(routed_ptr), p(capacity_ptr), p(peak_ptr), p(peak_edge_ptr), flags))
 
     def lfa_tables_device(self, pcost_all_ptr, dst_ptr, ndst, backup_ptr, backup_port_ptr,
                           kind_ptr, counts_ptr=0, link_only=False, timing=False):

@@ -45,7 +45,8 @@ __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "check_link_costs", "COST_INF", "COST_MAX", "COST_LDS_MAX_V", "COST_LDS_B8_MAX_V",
            "cost_ecmp_link_loads_host", "least_cost_paths_lex", "count_least_cost_paths",
            "COST_ECMP_LDS_MAX_V", "FAILURE_LDS_MAX_V", "normalise_scenarios",
-           "failure_ecmp_link_loads_host", "lfa_tables_host", "LFA_MAX_V", "LFA_BACKUP",
+           "failure_ecmp_link_loads_host", "normalise_cost_scenarios",
+           "whatif_ecmp_link_loads_host", "peak_utilisation", "lfa_tables_host", "LFA_MAX_V", "LFA_BACKUP",
            "LFA_DOWNSTREAM", "LFA_NODE"]
 
 # bytes of device tables one TableCache keeps per route mode before it
@@ -632,6 +633,119 @@ def failure_ecmp_link_loads_host(csr, cost, dsts, rows, srcs, weights=None, scen
     return load, lost, routed
 
 
+def normalise_cost_scenarios(scenarios, csr):
+    """Cost scenarios (a sequence of ``(edges, costs)``: CSR edge indices and
+    the cost each takes, COST_INF: the link is down) as the list of their
+    (int32 edges ascending, uint32 costs beside them).  A repeated edge, an
+    index outside [0, E), a list of another length and a cost that is neither
+    COST_INF nor one ``check_link_costs`` accepts (>= 1, times (V - 1) below
+    COST_INF) are ValueErrors."""
+    V, E = int(csr.V), int(csr.E)
+    out = []
+    for edges, costs in scenarios:
+        e = np.asarray(edges, np.int64).reshape(-1)
+        c = np.asarray(costs).reshape(-1)
+        if c.shape != e.shape:
+            raise ValueError("one cost per overridden link")
+        if c.size and c.dtype.kind not in "iu":
+            raise ValueError("link costs are integers")
+        for x in c.tolist():
+            if x != COST_INF and (x < 1 or x * max(0, V - 1) >= COST_INF):
+                raise ValueError("an override is COST_INF or a cost >= 1 with cost * (V - 1) "
+                                 "below COST_INF: %r" % (x,))
+        order = np.argsort(e, kind="stable")
+        e, c = e[order], c.astype(np.uint32)[order]
+        if e.size and (e[0] < 0 or e[-1] >= E):
+            raise ValueError("an overridden link is an edge index in [0, %d)" % E)
+        if (e[1:] == e[:-1]).any():
+            raise ValueError("a link is overridden once per scenario")
+        out.append((e.astype(np.int32), c))
+    return out
+
+
+def peak_utilisation(load, capacity=None):
+    """(peak float64, edge int): the largest ``load[e] / capacity[e]``
+    (capacity None: 1.0 each) and the first link that attains it; 0.0 and -1
+    when nothing is carried."""
+    u = np.asarray(load, np.float64)
+    if capacity is not None:
+        u = u / np.asarray(capacity, np.float64)
+    if u.size == 0 or not (u.max() > 0):
+        return 0.0, -1
+    return float(u.max()), int(u.argmax())
+
+
+def _check_capacity(capacity, E):
+    """float64 [E] capacities, every one finite and > 0, or None."""
+    if capacity is None:
+        return None
+    cap = np.ascontiguousarray(capacity, np.float64)
+    if cap.shape != (E,):
+        raise ValueError("one capacity per link of the graph (%d)" % E)
+    if not (np.isfinite(cap) & (cap > 0)).all():
+        raise ValueError("capacities are positive finite numbers")
+    return cap
+
+
+def whatif_ecmp_link_loads_host(csr, cost, dsts, rows, srcs, weights=None, scenarios=(),
+                                split="route", capacity=None):
+    """numpy restatement of sdnr_whatif_ecmp_link_loads (the CPU tests' engine
+    double and an independent check of whatif_loads.hip): (load float64 [nscen,
+    E], lost float64 [nscen], routed bool [nscen, npairs], peak float64
+    [nscen], peak_edge int32 [nscen]) of the pairs of
+    ``failure_ecmp_link_loads_host`` once per cost scenario of ``scenarios``
+    (``(edges, costs)``: the links of ``edges`` cost ``costs``, COST_INF: the
+    link is down; every other link keeps its cost of ``cost``, None: 1).
+    ``peak[k]``: the largest ``load[k, e] / capacity[e]`` (None: 1.0 each),
+    ``peak_edge[k]``: the first link that attains it (0.0 and -1 without load).
+
+    Deliberately not the kernel's cursor: per scenario the full cost vector is
+    built, the COST_INF edges are really removed from the CSR,
+    ``cost_tables_host`` and ``cost_ecmp_link_loads_host`` run on that graph
+    under those costs, and the loads are scattered back to the full graph's
+    edge order (a link that is down holds 0.0)."""
+    from .topologies import CSR
+    if split not in SPLITS:
+        raise ValueError("split must be 'route' or 'hop'")
+    V, E = int(csr.V), int(csr.E)
+    cost = np.ones(E, np.uint32) if cost is None else check_link_costs(csr, cost)
+    scen = normalise_cost_scenarios(scenarios, csr)
+    cap = _check_capacity(capacity, E)
+    dsts = np.asarray(dsts, np.int64)
+    rows = np.asarray(rows, np.int64)
+    srcs = np.asarray(srcs, np.int64)
+    n = int(rows.shape[0])
+    w = np.ones(n, np.uint64) if weights is None else np.asarray(weights, np.uint64)
+    load = np.zeros((len(scen), E), np.float64)
+    lost = np.zeros(len(scen), np.float64)
+    routed = np.zeros((len(scen), n), bool)
+    peak = np.zeros(len(scen), np.float64)
+    peak_edge = np.full(len(scen), -1, np.int32)
+    if n == 0 or dsts.size == 0:
+        return load, lost, routed, peak, peak_edge
+    if rows.min() < 0 or rows.max() >= dsts.shape[0]:
+        raise ValueError("whatif_ecmp_link_loads_host: a pair names a row outside dsts")
+    esrc = np.repeat(np.arange(V, dtype=np.int64), np.diff(np.asarray(csr.row_ptr, np.int64)))
+    d = dsts[rows]
+    s_ok = (srcs >= 0) & (srcs < V)
+    d_ok = (d >= 0) & (d < V)
+    sc = np.where(s_ok, srcs, 0)
+    for k, (edges, costs) in enumerate(scen):
+        now = cost.copy()
+        now[edges] = costs
+        keep = now != COST_INF
+        rp = np.zeros(V + 1, np.int64)
+        np.cumsum(np.bincount(esrc[keep], minlength=V), out=rp[1:])
+        red = CSR(csr.dpids, rp, np.asarray(csr.col)[keep], np.asarray(csr.port)[keep])
+        pc = cost_tables_host(red, now[keep], dsts)[0]
+        load[k, keep] = cost_ecmp_link_loads_host(red, now[keep], pc, rows, srcs, weights, split)
+        routed[k] = s_ok & d_ok & (pc[rows, sc] != COST_INF)
+        gone = s_ok & (srcs != d) & (w > 0) & ~routed[k]
+        lost[k] = float(w[gone].astype(np.float64).sum())
+        peak[k], peak_edge[k] = peak_utilisation(load[k], cap)
+    return load, lost, routed, peak, peak_edge
+
+
 LFA_MAX_V = 16384               # csrc/common.h kLfaMaxV: sdnr_lfa_tables' cap (sdnr_apsp's)
 LFA_BACKUP, LFA_DOWNSTREAM, LFA_NODE = 1, 2, 4     # bits of sdnr_lfa_tables' kind
 
@@ -1214,6 +1328,118 @@ class RouteEngine(object):
         else:
             routed[:, order] = got
         return load, d_lost.cpu().numpy(), routed
+
+    def whatif_ecmp_link_loads(self, export, cost, dsts, rows, srcs, weights=None, scenarios=(),
+                               split="route", capacity=None, loads=True, reach=True,
+                               timing=False, table_budget=None):
+        """Link-cost what-if (whatif_loads.hip, sdnr_whatif_ecmp_link_loads):
+        the loads of ``cost_ecmp_link_loads`` once per cost scenario, nothing
+        uploaded or cached changing: (load float64 [nscen, E], lost float64
+        [nscen], routed bool [nscen, npairs], peak float64 [nscen], peak_edge
+        int32 [nscen]) on the host.
+
+        ``cost``, ``dsts``, ``rows``, ``srcs``, ``weights``, ``split`` as in
+        ``failure_ecmp_link_loads``.  ``scenarios``: a list of ``(edges,
+        costs)`` -- CSR edge indices and the cost each takes in that scenario,
+        COST_INF: the link is down -- checked and sorted here
+        (``normalise_cost_scenarios``).  ``capacity``: float64 [E] or None (1.0
+        per link); ``peak[k]`` is the largest ``load[k, e] / capacity[e]`` and
+        ``peak_edge[k]`` the first link that attains it (0.0 and -1 without
+        load), reduced on the device.
+
+        The scenarios are processed in chunks whose load planes fit
+        ``table_budget`` bytes (None: DEFAULT_TABLE_BUDGET), 8 E + npairs bytes
+        per scenario, in one device buffer reused across the chunks.
+        ``loads=False``: the planes never leave the device; load and routed
+        come back as None -- what a search over costs needs is one number per
+        candidate.  ``reach=False``: lost and routed are not computed (finite
+        costs never change reachability) and come back as None.  Sums are f64
+        atomics: equal to ``whatif_ecmp_link_loads_host`` within rounding, not
+        bit-reproducible."""
+        if split not in SPLITS:
+            raise ValueError("split must be 'route' or 'hop'")
+        if cost is None:
+            self.load(export)
+            if self._costs is not None:
+                self._costs = None
+                self.ctx.set_link_costs(None)
+        else:
+            self.set_link_costs(export, cost)
+        t = self._torch
+        V, E = int(export.csr.V), int(export.csr.E)
+        scen = normalise_cost_scenarios(scenarios, export.csr)
+        cap = _check_capacity(capacity, E)
+        nscen = len(scen)
+        rows = np.asarray(rows, np.int64)
+        n = int(rows.shape[0])
+        d = np.asarray(dsts, np.int64)
+        nrows = int(d.shape[0])
+        load = np.zeros((nscen, E), np.float64) if loads else None
+        lost = np.zeros(nscen, np.float64) if reach else None
+        routed = np.zeros((nscen, n), bool) if loads and reach else None
+        peak = np.zeros(nscen, np.float64)
+        peak_edge = np.full(nscen, -1, np.int32)
+        if n == 0 or nrows == 0 or nscen == 0 or V == 0:
+            return load, lost, routed, peak, peak_edge
+        if rows.min() < 0 or rows.max() >= nrows:
+            raise ValueError("whatif_ecmp_link_loads: a pair names a row outside dsts")
+        order, off = _pairs_by_row(rows, nrows)
+        s = np.asarray(srcs, np.int64)[order]
+        s = np.where((s < 0) | (s >= V), -1, s).astype(np.int32)
+        d = np.where((d < 0) | (d >= V), -1, d).astype(np.int32)
+        d_dst = t.from_numpy(d).to(self.dev)
+        d_off = t.from_numpy(off).to(self.dev)
+        d_src = t.from_numpy(s).to(self.dev)
+        d_w = d_cap = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights, np.uint64)[order])
+            d_w = t.from_numpy(w.view(np.int64)).to(self.dev)
+        if cap is not None:
+            d_cap = t.from_numpy(cap).to(self.dev)
+        budget = DEFAULT_TABLE_BUDGET if table_budget is None else int(table_budget)
+        step = min(nscen, max(1, budget // max(1, 8 * E + n)))
+        d_load = t.empty((step, max(E, 1)), dtype=t.float64, device=self.dev)
+        d_lost = t.empty(step, dtype=t.float64, device=self.dev) if reach else None
+        d_routed = t.empty((step, n), dtype=t.uint8, device=self.dev) if routed is not None \
+            else None
+        d_peak = t.empty(step, dtype=t.float64, device=self.dev)
+        d_pedge = t.empty(step, dtype=t.int32, device=self.dev)
+        ptr = lambda a: a.data_ptr() if a is not None else 0     # noqa: E731
+        self._ready()
+        for c0 in range(0, nscen, step):
+            part = scen[c0:c0 + step]
+            m = len(part)
+            soff = np.zeros(m + 1, np.int64)
+            np.cumsum([a.shape[0] for a, _ in part], out=soff[1:])
+            edges = np.concatenate([a for a, _ in part] + [np.zeros(1, np.int32)])
+            costs = np.concatenate([c for _, c in part] + [np.zeros(1, np.uint32)])
+            d_soff = t.from_numpy(soff).to(self.dev)
+            d_edges = t.from_numpy(edges.astype(np.int32)).to(self.dev)
+            d_costs = t.from_numpy(costs.astype(np.uint32).view(np.int32)).to(self.dev)
+            d_load.zero_()
+            if d_lost is not None:
+                d_lost.zero_()
+            if d_routed is not None:
+                d_routed.zero_()
+            self.ctx.whatif_ecmp_link_loads_device(
+                d_dst.data_ptr(), nrows, d_off.data_ptr(), d_src.data_ptr(), ptr(d_w), m,
+                d_soff.data_ptr(), d_edges.data_ptr(), d_costs.data_ptr(), d_load.data_ptr(),
+                ptr(d_lost), ptr(d_routed), ptr(d_cap), d_peak.data_ptr(), d_pedge.data_ptr(),
+                hop=split == "hop", timing=timing)
+            self.ctx.synchronize()          # raises on a bad override list or capacity
+            peak[c0:c0 + m] = d_peak[:m].cpu().numpy()
+            peak_edge[c0:c0 + m] = d_pedge[:m].cpu().numpy()
+            if reach:
+                lost[c0:c0 + m] = d_lost[:m].cpu().numpy()
+            if loads:
+                load[c0:c0 + m] = d_load[:m, :E].cpu().numpy()
+            if routed is not None:
+                got = d_routed[:m].cpu().numpy().astype(bool)
+                if isinstance(order, slice):
+                    routed[c0:c0 + m] = got
+                else:
+                    routed[c0:c0 + m][:, order] = got
+        return load, lost, routed, peak, peak_edge
 
     def lfa_tables(self, export, cost, pcost_all, dsts, link_only=False, timing=False):
         """Loop-free alternate next hops (lfa_tables.hip, sdnr_lfa_tables):

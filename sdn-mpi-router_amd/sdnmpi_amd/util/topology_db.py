@@ -26,8 +26,9 @@ first route query raises (``sdnmpi_amd._native.NativeUnavailable`` /
 
 import numpy as np
 
-from ..engine import (COST_MAX, DEFAULT_TABLE_BUDGET, INT32, LFA_MAX_V, RouteEngine, TableCache, _gather,
+from ..engine import (COST_INF, COST_MAX, DEFAULT_TABLE_BUDGET, INT32, LFA_MAX_V, RouteEngine, TableCache, _gather,
                       _host, _take, _torch, _u16, check_link_costs, least_cost_paths_lex,
+                      peak_utilisation,
                       shortest_paths_lex, tree_path)
 from ..graph import TrackedDict, Versions, export_graph, update_export
 from ..incremental import edge_diff
@@ -37,7 +38,8 @@ try:   # the reference takes OFPP_LOCAL from Ryu's OpenFlow 1.0 module (:5)
 except Exception:   # noqa: BLE001 - Ryu is not a dependency of the engine
     OFPP_LOCAL = 0xfffe
 
-__all__ = ["TopologyDB", "LinkLoads", "SplitLinkLoads", "FailureLoads", "OFPP_LOCAL",
+__all__ = ["TopologyDB", "LinkLoads", "SplitLinkLoads", "FailureLoads", "CostChangeLoads",
+           "CostTuning", "OFPP_LOCAL",
            "sdn_mpi_mac"]
 
 _INF = 0xFFFF
@@ -166,6 +168,41 @@ class FailureLoads(object):
         return {(d, p): (x, k) for d, p, x, k in
                 zip(self.base.src_dpid[nz].tolist(), self.base.port[nz].tolist(),
                     top[nz].tolist(), at[nz].tolist())}
+
+
+class CostChangeLoads(FailureLoads):
+    """Predicted traffic per link under each of a list of link-cost scenarios
+    (:meth:`TopologyDB.cost_change_link_loads`): everything of
+    :class:`FailureLoads`, with ``scenarios`` holding per scenario the tuple
+    of its changes ``((src_dpid, dst_dpid), cost)`` that name existing links,
+    in the CSR's link order (``cost`` None: the link is down).
+
+    ``peak``: float64 [nscen], the largest utilisation ``load / capacity`` over
+    the switch links (last hops are not links of the fabric) in scenario k;
+    ``peak_link``: the first ``(src_dpid, dst_dpid)`` in link order that
+    attains it, None where nothing is carried; ``base_peak``: the peak of the
+    intact fabric."""
+
+    def __init__(self, scenarios, load, lost, base, hkey, hload, result, peak, peak_link,
+                 base_peak):
+        FailureLoads.__init__(self, scenarios, load, lost, base, hkey, hload, result)
+        self.peak = peak
+        self.peak_link = peak_link
+        self.base_peak = base_peak
+
+
+class CostTuning(object):
+    """What :meth:`TopologyDB.tune_link_costs` found.  ``costs``: the changed
+    costs ``{(src_dpid, dst_dpid): cost}``; ``peak_before`` / ``peak_after``:
+    the peak utilisation under the costs in force and with ``costs`` on top of
+    them; ``history``: per accepted step ``((src_dpid, dst_dpid), cost,
+    peak)``."""
+
+    def __init__(self, costs, peak_before, peak_after, history):
+        self.costs = costs
+        self.peak_before = peak_before
+        self.peak_after = peak_after
+        self.history = history
 
 
 def _weights(weights, n):
@@ -1363,6 +1400,43 @@ class TopologyDB(object):
             edges.append(es)
         return scen, edges
 
+    @staticmethod
+    def _scenario_last_hops(routed, w, dv, last, ok, inv):
+        """(hkey, hload uint64 [nscen, k], lost uint64 [nscen]) of MAC pairs
+        under scenarios: the last hops of the pairs whose switch pair is
+        routed in scenario k, and the weight of the known pairs that are not
+        (``w``, ``dv``, ``last``, ``ok``, ``inv`` from :meth:`_switch_pairs`)."""
+        nscen = routed.shape[0]
+        hkey, hinv = np.unique(np.stack([dv[ok], last[ok]], 1), axis=0, return_inverse=True)
+        hkey, hinv = hkey.reshape(-1, 2), hinv.reshape(-1)
+        hload = np.zeros((nscen, hkey.shape[0]), np.uint64)
+        lost = np.zeros(nscen, np.uint64)
+        for k in range(nscen):
+            got = routed[k][inv] if ok.size else np.zeros(0, bool)
+            np.add.at(hload[k], hinv[got], w[ok][got])
+            lost[k] = w[ok][~got].sum(dtype=np.uint64)
+        return hkey, hload, lost
+
+    def _all_pairs_scenario_last_hops(self, ex, routed, hv, hc, w):
+        """:meth:`_scenario_last_hops` of the all-host-pairs demand (switch
+        pairs ``repeat(hv) x tile(hv)`` with weights ``w``), from the per-switch
+        host counts ``hc``."""
+        nscen, n = routed.shape[0], hv.shape[0]
+        hd = np.asarray([ex.index[h.port.dpid] for h in self.hosts.values()], np.int64)
+        hp = np.asarray([int(h.port.port_no) for h in self.hosts.values()], np.int64)
+        hkey, hinv = np.unique(np.stack([hd, hp], 1).reshape(-1, 2), axis=0, return_inverse=True)
+        hkey, hinv = hkey.reshape(-1, 2), hinv.reshape(-1)
+        hload = np.zeros((nscen, hkey.shape[0]), np.uint64)
+        lost = np.zeros(nscen, np.uint64)
+        for k in range(nscen):
+            # hosts that reach switch d: every host on d gets that many flows, less itself
+            cnt = (routed[k].reshape(n, n) * hc[hv][:, None]).sum(0)
+            into = np.zeros(int(ex.csr.V), np.int64)
+            into[hv] = cnt - 1
+            np.add.at(hload[k], hinv, into[hd].astype(np.uint64))
+            lost[k] = w[~routed[k]].sum(dtype=np.uint64)
+        return hkey, hload, lost
+
     def _failure_switch_loads(self, ex, edges, sv, dv, w, split):
         """(load float64 [nscen, E], routed bool [nscen, n]) of switch pairs
         (dense ids sv -> dv, weights w u64) per failure scenario: one
@@ -1418,14 +1492,7 @@ class TopologyDB(object):
         scen, edges = self._failure_edges(ex, failures)
         w, dv, last, ok, inv, ssv, sdv, sw = self._switch_pairs(ex, pairs, weights)
         load, routed = self._failure_switch_loads(ex, edges, ssv, sdv, sw, split)
-        hkey, hinv = np.unique(np.stack([dv[ok], last[ok]], 1), axis=0, return_inverse=True)
-        hkey, hinv = hkey.reshape(-1, 2), hinv.reshape(-1)
-        hload = np.zeros((len(scen), hkey.shape[0]), np.uint64)
-        lost = np.zeros(len(scen), np.uint64)
-        for k in range(len(scen)):
-            got = routed[k][inv] if ok.size else np.zeros(0, bool)
-            np.add.at(hload[k], hinv[got], w[ok][got])
-            lost[k] = w[ok][~got].sum(dtype=np.uint64)
+        hkey, hload, lost = self._scenario_last_hops(routed, w, dv, last, ok, inv)
         base = self.least_cost_ecmp_link_loads(pairs, weights, split)
         return FailureLoads(
             scen, load, lost, base, hkey, hload,
@@ -1441,25 +1508,9 @@ class TopologyDB(object):
                 failures, [(a, b) for a in macs for b in macs if a != b], None, split)
         ex = self.graph()
         scen, edges = self._failure_edges(ex, failures)
-        hv = np.asarray(self._host_vertices(ex), np.int64)
-        hc = np.asarray(ex.host_count, np.int64)
-        n = hv.shape[0]
-        sv, dv = np.repeat(hv, n), np.tile(hv, n)
-        w = (hc[sv] * (hc[dv] - (sv == dv))).astype(np.uint64)
+        sv, dv, w, hv, hc = self._all_pairs_demand(ex)
         load, routed = self._failure_switch_loads(ex, edges, sv, dv, w, split)
-        hd = np.asarray([ex.index[h.port.dpid] for h in self.hosts.values()], np.int64)
-        hp = np.asarray([int(h.port.port_no) for h in self.hosts.values()], np.int64)
-        hkey, hinv = np.unique(np.stack([hd, hp], 1).reshape(-1, 2), axis=0, return_inverse=True)
-        hkey, hinv = hkey.reshape(-1, 2), hinv.reshape(-1)
-        hload = np.zeros((len(scen), hkey.shape[0]), np.uint64)
-        lost = np.zeros(len(scen), np.uint64)
-        for k in range(len(scen)):
-            # hosts that reach switch d: every host on d gets that many flows, less itself
-            cnt = (routed[k].reshape(n, n) * hc[hv][:, None]).sum(0)
-            into = np.zeros(int(ex.csr.V), np.int64)
-            into[hv] = cnt - 1
-            np.add.at(hload[k], hinv, into[hd].astype(np.uint64))
-            lost[k] = w[~routed[k]].sum(dtype=np.uint64)
+        hkey, hload, lost = self._all_pairs_scenario_last_hops(ex, routed, hv, hc, w)
         base = self.all_pairs_least_cost_ecmp_link_loads(split)
         return FailureLoads(
             scen, load, lost, base, hkey, hload,
@@ -1470,6 +1521,261 @@ class TopologyDB(object):
         :meth:`mpi_link_loads`)."""
         pairs, weights = self._rank_pairs(rank_to_mac, traffic)
         return self.failure_link_loads(failures, pairs, weights, split)
+
+    # -- link-cost what-if and the cost tuner -----------------------------
+    @staticmethod
+    def _link_edge(ex, a, b):
+        """The CSR edge index of the link a -> b (dpids), None if there is none."""
+        u, v = ex.index.get(a), ex.index.get(b)
+        if u is None or v is None:
+            return None
+        rp, col = ex.csr.row_ptr, ex.csr.col
+        lo, hi = int(rp[u]), int(rp[u + 1])
+        e = lo + int(np.searchsorted(col[lo:hi], v))
+        return e if e < hi and int(col[e]) == v else None
+
+    @staticmethod
+    def _edge_links(ex):
+        """[(src_dpid, dst_dpid)] of every CSR edge, as a function of the edge."""
+        csr = ex.csr
+        esrc = np.repeat(np.arange(int(csr.V)), np.diff(np.asarray(csr.row_ptr, np.int64)))
+        dp = csr.dpids
+        return lambda e: (int(dp[esrc[e]]), int(dp[csr.col[e]]))
+
+    def _cost_changes(self, ex, changes):
+        """(scenarios, overrides): per scenario the tuple of its changes
+        ``((src_dpid, dst_dpid), cost or None)`` on existing links in CSR
+        order, and ``(edges int32, costs uint32)`` for the engine (None ->
+        COST_INF).  A cost outside :meth:`set_link_cost`'s rule or one that
+        reaches COST_INF times (V - 1), and a link given twice, are
+        ValueErrors."""
+        V = int(ex.csr.V)
+        link = self._edge_links(ex)
+        scen, over = [], []
+        for sc in changes:
+            seen, got = set(), {}
+            for key, c in (sc.items() if hasattr(sc, "items") else sc):
+                if not isinstance(key, tuple) or len(key) != 2:
+                    raise ValueError("cost changes are keyed by (src_dpid, dst_dpid): %r" % (key,))
+                if key in seen:
+                    raise ValueError("link %r is given twice in one scenario" % (key,))
+                seen.add(key)
+                if c is not None:
+                    if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or \
+                            not 1 <= int(c) <= COST_MAX:
+                        raise ValueError("link cost of %r must be an int in [1, 2**32 - 2] or "
+                                         "None (down): %r" % (key, c))
+                    if int(c) * max(0, V - 1) >= COST_INF:
+                        raise ValueError("cost %d * (V - 1) reaches COST_INF" % int(c))
+                e = self._link_edge(ex, key[0], key[1])
+                if e is not None:
+                    got[e] = COST_INF if c is None else int(c)
+            es = sorted(got)
+            scen.append(tuple((link(e), None if got[e] == COST_INF else got[e]) for e in es))
+            over.append((np.asarray(es, np.int32), np.asarray([got[e] for e in es], np.uint32)))
+        return scen, over
+
+    def _capacity_vector(self, ex, capacity):
+        """float64 [E] capacities in CSR edge order from ``{(src_dpid,
+        dst_dpid): positive number}`` (links not named: 1.0; links that do not
+        exist are ignored), or None when none is given."""
+        if capacity is None:
+            return None
+        cap = np.ones(int(ex.csr.E), np.float64)
+        for key, x in dict(capacity).items():
+            if not isinstance(key, tuple) or len(key) != 2:
+                raise ValueError("capacities are keyed by (src_dpid, dst_dpid): %r" % (key,))
+            if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) \
+                    or not (float(x) > 0 and np.isfinite(float(x))):
+                raise ValueError("capacity of %r must be a positive finite number: %r" % (key, x))
+            e = self._link_edge(ex, key[0], key[1])
+            if e is not None:
+                cap[e] = float(x)
+        return cap
+
+    def _cost_change_switch_loads(self, ex, over, sv, dv, w, split, cap, loads=True, reach=True):
+        """The engine's (load, lost, routed, peak, peak_edge) of switch pairs
+        (dense ids sv -> dv, weights w u64) per cost scenario: one
+        sdnr_whatif_ecmp_link_loads call per chunk of scenarios whose planes
+        fit the table budget."""
+        if split not in ("route", "hop"):
+            raise ValueError("split must be 'route' or 'hop'")
+        dsts, rows = np.unique(dv, return_inverse=True)
+        return self.engine.whatif_ecmp_link_loads(
+            ex, self._cost_vector(ex), dsts, rows.reshape(-1), sv, w, over, split, cap,
+            loads=loads, reach=reach, table_budget=self._budget)
+
+    def _cost_change_result(self, ex, scen, load, lost, base, hkey, hload, peak, pedge, cap):
+        link = self._edge_links(ex)
+        return CostChangeLoads(
+            scen, load, lost, base, hkey, hload,
+            lambda ld, hk, hl: self._link_loads_result(ex, ld, hk, hl, SplitLinkLoads),
+            peak, [link(e) if e >= 0 else None for e in pedge.tolist()],
+            peak_utilisation(base.load, cap)[0])
+
+    def cost_change_link_loads(self, changes, pairs, weights=None, split="route", capacity=None):
+        """What every link carries if link costs change: :meth:`least_cost_
+        ecmp_link_loads` of the pairs once per scenario of ``changes``, as a
+        :class:`CostChangeLoads` -- cost a hot link up, or a link out for
+        maintenance, and see the loads before anything is installed.  A
+        scenario is a mapping or an iterable of ``((src_dpid, dst_dpid),
+        cost)``: ``cost`` an int under :meth:`set_link_cost`'s rule, or None
+        for link down; every link not named keeps the cost in force.  Links
+        that do not exist are ignored, a link given twice in one scenario is a
+        ValueError, the empty scenario is the fabric as it is.  ``capacity``:
+        ``{(src_dpid, dst_dpid): positive number}`` for the peak utilisation,
+        links not named have capacity 1.0.
+
+        Defining property: ``cost_change_link_loads(C, pairs, w, split)
+        .scenario(k).as_dict()`` equals ``least_cost_ecmp_link_loads(pairs, w,
+        split).as_dict()`` of a second ``TopologyDB`` on which the changes of
+        ``C[k]`` were really made with ``set_link_cost`` / ``delete_link`` --
+        within rounding, and exactly where every share is a power of two.
+        ``lost`` and the last hops as in :meth:`failure_link_loads`.
+
+        Nothing of this object changes: not ``links``, the export, the cost
+        settings, the cached tables or the graph on the GPU.  One kernel
+        (whatif_loads.hip) recomputes the least costs of every (scenario,
+        destination switch) under the scenario's costs and pushes the demand
+        down that least-cost DAG; the peaks are reduced on the device."""
+        pairs = list(pairs)
+        weights = None if weights is None else list(weights)
+        ex = self.graph()
+        scen, over = self._cost_changes(ex, changes)
+        cap = self._capacity_vector(ex, capacity)
+        w, dv, last, ok, inv, ssv, sdv, sw = self._switch_pairs(ex, pairs, weights)
+        load, _, routed, peak, pedge = self._cost_change_switch_loads(ex, over, ssv, sdv, sw,
+                                                                     split, cap)
+        hkey, hload, lost = self._scenario_last_hops(routed, w, dv, last, ok, inv)
+        base = self.least_cost_ecmp_link_loads(pairs, weights, split)
+        return self._cost_change_result(ex, scen, load, lost, base, hkey, hload, peak, pedge, cap)
+
+    def all_pairs_cost_change_link_loads(self, changes, split="route", capacity=None):
+        """:meth:`cost_change_link_loads` over every ordered pair of distinct
+        hosts with weight 1, from the per-switch host counts (as
+        :meth:`all_pairs_link_loads`)."""
+        if any(self._mac_to_int(m) in self.switches for m in self.hosts):
+            macs = list(self.hosts)
+            return self.cost_change_link_loads(
+                changes, [(a, b) for a in macs for b in macs if a != b], None, split, capacity)
+        ex = self.graph()
+        scen, over = self._cost_changes(ex, changes)
+        cap = self._capacity_vector(ex, capacity)
+        sv, dv, w, hv, hc = self._all_pairs_demand(ex)
+        load, _, routed, peak, pedge = self._cost_change_switch_loads(ex, over, sv, dv, w, split,
+                                                                     cap)
+        hkey, hload, lost = self._all_pairs_scenario_last_hops(ex, routed, hv, hc, w)
+        base = self.all_pairs_least_cost_ecmp_link_loads(split)
+        return self._cost_change_result(ex, scen, load, lost, base, hkey, hload, peak, pedge, cap)
+
+    def mpi_cost_change_link_loads(self, changes, rank_to_mac, traffic=None, split="route",
+                                   capacity=None):
+        """:meth:`cost_change_link_loads` of an MPI job (``traffic`` as in
+        :meth:`mpi_link_loads`)."""
+        pairs, weights = self._rank_pairs(rank_to_mac, traffic)
+        return self.cost_change_link_loads(changes, pairs, weights, split, capacity)
+
+    def _all_pairs_demand(self, ex):
+        """(sv, dv, w, hv, hc): the all-host-pairs demand as switch pairs --
+        hosts(s) * hosts(d) from s to d, less the hosts themselves."""
+        hv = np.asarray(self._host_vertices(ex), np.int64)
+        hc = np.asarray(ex.host_count, np.int64)
+        n = hv.shape[0]
+        sv, dv = np.repeat(hv, n), np.tile(hv, n)
+        return sv, dv, (hc[sv] * (hc[dv] - (sv == dv))).astype(np.uint64), hv, hc
+
+    def _tune(self, ex, sv, dv, w, capacity, split, rounds, top, steps, apply):
+        """:meth:`tune_link_costs` on switch pairs (dense ids sv -> dv, weights
+        w u64)."""
+        steps = [int(x) for x in steps]
+        if int(top) < 1 or not steps or min(steps) < 1:
+            raise ValueError("top and every step are positive integers")
+        cap = self._capacity_vector(ex, capacity)
+        base = self._cost_vector(ex)
+        V, E = int(ex.csr.V), int(ex.csr.E)
+        link = self._edge_links(ex)
+        accepted, history = {}, []          # edge -> cost; (link, cost, peak)
+        peak_before = peak_after = None
+
+        def scenario(extra=()):
+            now = dict(accepted)
+            now.update(extra)
+            es = sorted(now)
+            return np.asarray(es, np.int32), np.asarray([now[e] for e in es], np.uint32)
+
+        def run(scen, loads):
+            return self._cost_change_switch_loads(ex, scen, sv, dv, w, split, cap, loads=loads,
+                                                  reach=False)
+
+        for _ in range(max(0, int(rounds))):
+            # the hottest links under the changes accepted so far
+            util = run([scenario()], True)[0][0]
+            if cap is not None:
+                util = util / cap
+            hot = [int(e) for e in np.lexsort((np.arange(E), -util))[:int(top)] if util[e] > 0]
+            cands = [(e, c) for e in hot for c in (accepted.get(e, int(base[e])) + s for s in steps)
+                     if c * max(0, V - 1) < COST_INF]
+            peaks = run([scenario()] + [scenario([c]) for c in cands], False)[3]
+            if peak_before is None:
+                peak_before = peak_after = float(peaks[0])
+            if not cands:
+                break
+            m = float(peaks[1:].min())
+            if not m < float(peaks[0]) * (1 - 1e-9):
+                break
+            i = int(np.nonzero(peaks[1:] <= m * (1 + 1e-9))[0][0])
+            e, c = cands[i]
+            accepted[e] = c
+            peak_after = float(peaks[1 + i])
+            history.append((link(e), c, peak_after))
+        if peak_before is None:
+            peak_before = peak_after = float(run([scenario()], False)[3][0])
+        costs = {link(e): c for e, c in sorted(accepted.items())}
+        if apply and costs:
+            self.set_link_costs(costs)
+        return CostTuning(costs, peak_before, peak_after, history)
+
+    def tune_link_costs(self, pairs, weights=None, capacity=None, split="route", rounds=8, top=8,
+                        steps=(1, 2, 4), apply=False):
+        """Which cost, on which link, flattens the fabric: a deterministic
+        greedy descent on the peak utilisation (``load / capacity`` over the
+        switch links, ``capacity`` as in :meth:`cost_change_link_loads`) of
+        the pairs' :meth:`least_cost_ecmp_link_loads`, as a :class:`CostTuning`.
+
+        Each of at most ``rounds`` rounds takes the ``top`` most utilised links
+        under the changes accepted so far (ties by link order) and evaluates,
+        for each of them and each step of ``steps``, "the accepted changes
+        plus this link at its current cost + step" -- all of them, and the
+        accepted changes alone, as the scenarios of one what-if call that
+        returns only the peaks.  Candidates whose cost would break the cost
+        rule are left out.  With m the smallest candidate peak, the first
+        candidate in link-then-step order whose peak is <= m (1 + 1e-9) is
+        accepted if m < the current peak (1 - 1e-9); otherwise the descent
+        stops.  ``apply=True`` ends with one ``set_link_costs(costs)``; by
+        default nothing of this object changes."""
+        ex = self.graph()
+        _, _, _, _, _, sv, dv, sw = self._switch_pairs(ex, list(pairs), weights)
+        return self._tune(ex, sv, dv, sw, capacity, split, rounds, top, steps, apply)
+
+    def all_pairs_tune_link_costs(self, capacity=None, split="route", rounds=8, top=8,
+                                  steps=(1, 2, 4), apply=False):
+        """:meth:`tune_link_costs` over every ordered pair of distinct hosts
+        with weight 1, from the per-switch host counts (as
+        :meth:`all_pairs_link_loads`)."""
+        if any(self._mac_to_int(m) in self.switches for m in self.hosts):
+            macs = list(self.hosts)
+            return self.tune_link_costs([(a, b) for a in macs for b in macs if a != b], None,
+                                        capacity, split, rounds, top, steps, apply)
+        ex = self.graph()
+        sv, dv, w, _, _ = self._all_pairs_demand(ex)
+        return self._tune(ex, sv, dv, w, capacity, split, rounds, top, steps, apply)
+
+    def mpi_tune_link_costs(self, rank_to_mac, traffic=None, capacity=None, split="route",
+                            rounds=8, top=8, steps=(1, 2, 4), apply=False):
+        """:meth:`tune_link_costs` of an MPI job (``traffic`` as in
+        :meth:`mpi_link_loads`)."""
+        pairs, weights = self._rank_pairs(rank_to_mac, traffic)
+        return self.tune_link_costs(pairs, weights, capacity, split, rounds, top, steps, apply)
 
     def find_routes(self, pairs, multiple=False):
         """find_route over many (src_mac, dst_mac) pairs; tables are computed
