@@ -603,6 +603,52 @@ int sdnr_lfa_tables(sdnr_ctx *ctx, const uint32_t *pcost_all, const int32_t *dst
                     int32_t *backup, int32_t *backup_port, uint8_t *kind, uint32_t *counts,
                     uint32_t flags);
 
+/* Least-loaded routes: per destination, inside the least-cost (ECMP) set, the
+ * route whose busiest link is the least busy -- the controller's question
+ * "given what the links carry now, which of the equal-cost routes should this
+ * flow take".  Integer and bit-exact.
+ *   pcost  [ndst][V] u32 rows as sdnr_cost_tables writes them under the costs
+ *          in force (sdnr_graph_costs; none uploaded: every link costs 1 and
+ *          the rows are hop counts), row i toward dst[i];
+ *   util   [E] u32, the utilisation of every directed link in the uploaded
+ *          CSR's edge order, in any unit, values in [0, 0xFFFFFFFE] (from host
+ *          buffers a 0xFFFFFFFF is SDNR_ERR_INVAL; a device one reads as
+ *          0xFFFFFFFE);
+ *   bott, nh, nh_port [ndst][V]: WRITTEN.
+ * Link e = (x -> n) is tight when pcost[n] != SDNR_COST_INF and pcost[n] +
+ * cost[e] == pcost[x]: the links of the least-cost routes toward dst[i].
+ *   bott[i*V+x]     min over tight e = (x -> n) of max(util[e], bott[n]); 0 at
+ *                   dst[i], 0xFFFFFFFF where pcost[x] is SDNR_COST_INF: the
+ *                   smallest achievable busiest-link utilisation over all
+ *                   least-cost routes x -> dst[i];
+ *   nh[i*V+x]       the n of the tight link with the smallest key
+ *                   (max(util[e], bott[n]), util[e], n), compared
+ *                   lexicographically -- the best bottleneck, then the emptier
+ *                   first link, then the smaller neighbour (-1 for x == dst[i]
+ *                   or unreachable);
+ *   nh_port[i*V+x]  that link's port, links[x][nh].src.port_no.
+ * Following nh from x gives a least-cost route whose busiest link carries
+ * exactly bott[x].  A tight link lowers pcost strictly (costs are >= 1), so an
+ * nh row is an in-tree toward dst[i] and sdnr_link_loads with
+ * SDNR_LOADS_TO_ROOT takes it as it is.  With util all zero, or all equal, nh
+ * and nh_port equal sdnr_cost_tables' bit for bit.  A link that is not tight
+ * is never used, however empty it is.  nh and nh_port go together and may both
+ * be NULL (bottlenecks only).
+ * Host buffers: synchronous; SDNR_DEVICE_PTRS: asynchronous on the context's
+ * stream; SDNR_TIMING as in sdnr_cost_tables.  Without an uploaded graph:
+ * SDNR_ERR_STATE.  ndst == 0: SDNR_OK, nothing touched.  A destination outside
+ * [0, V): SDNR_ERR_INVAL for host buffers (the ids are checked before anything
+ * runs), an empty row (0xFFFFFFFF / -1 / -1, its pcost row not read) for
+ * device ids.  One launch (pull sweeps over the tight links to the fixed
+ * point: depth of the least-cost DAG + 1 of them); on a multi-device context
+ * it runs on the primary device.  A requested row with pcost[dst[i]] != 0, or
+ * with a vertex of finite cost > 0 that has no tight link, is reported by
+ * sdnr_synchronize as SDNR_ERR_INVAL; the other rows of the call are
+ * unaffected. */
+int sdnr_widest_tables(sdnr_ctx *ctx, const uint32_t *pcost, const uint32_t *util,
+                       const int32_t *dst, int32_t ndst, uint32_t *bott, int32_t *nh,
+                       int32_t *nh_port, uint32_t flags);
+
 /* Flood ports (TopologyManager._is_edge_port / _do_broadcast, reference
  * sdnmpi/topology.py:150-177): is_edge[i] = 1 iff ports[i] is neither end of
  * any link.  Keys are (dense switch id << 32) | port_no; ends (both ends of

@@ -85,6 +85,11 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "not a least-cost labelling of the uploaded graph under the costs in "
                              "force (P[d][d] != 0, or a vertex of finite cost > 0 without a tight "
                              "link): that row invalid");
+        if (h & kErrWidest)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_widest_tables: a requested pcost row is not a "
+                             "least-cost labelling of the uploaded graph under the costs in force "
+                             "(pcost[d] != 0, a vertex of finite cost > 0 without a tight route "
+                             "to d, or sweeps that outran V): that row invalid");
         if (h & kErrCostTables)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_tables: V relaxation sweeps did not reach "
                              "the fixed point (link costs outside what sdnr_graph_costs accepts): "
@@ -1531,6 +1536,48 @@ int sdnr_lfa_tables(sdnr_ctx *ctx, const uint32_t *pcost_all, const int32_t *dst
     ctx->timed = (flags & SDNR_TIMING) != 0;
     return sdnr_launch_lfa_tables(ctx, pcost_all, dst, ndst, backup, backup_port, kind, counts,
                                   (flags & SDNR_LFA_LINK_ONLY) != 0);
+}
+
+int sdnr_widest_tables(sdnr_ctx *ctx, const uint32_t *pcost, const uint32_t *util,
+                       const int32_t *dst, int32_t ndst, uint32_t *bott, int32_t *nh,
+                       int32_t *nh_port, uint32_t flags)
+{
+    int rc = begin_call(ctx, ndst, dst, flags, "sdnr_widest_tables");
+    if (rc) return rc;
+    if (ndst > 0 && (!pcost || !bott || (ctx->E > 0 && !util)))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_widest_tables: null pointer");
+    if ((nh == nullptr) != (nh_port == nullptr))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_widest_tables: nh and nh_port go together");
+    if (ndst == 0 || ctx->V == 0) return SDNR_OK;
+    if (flags & SDNR_DEVICE_PTRS)
+        return sdnr_launch_widest_tables(ctx, pcost, util, dst, ndst, bott, nh, nh_port);
+    const size_t E = (size_t)ctx->E;
+    for (size_t e = 0; e < E; ++e)
+        if (util[e] == 0xFFFFFFFFu)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_widest_tables: util[%zu] is 0xFFFFFFFF "
+                             "(utilisations are at most 0xFFFFFFFE)", e);
+    // host buffers: stage the ids, the pcost rows, util and the tables on the primary device
+    const size_t n = (size_t)ndst * (size_t)ctx->V * 4;
+    size_t need = 4 * (size_t)ndst + 256 + 4 * E + 256 + (n + 256) * (nh ? 4 : 2);
+    if ((rc = sdnr_reserve(&ctx->stage, &ctx->stage_bytes, need))) return rc;
+    Stage st{static_cast<char *>(ctx->stage)};
+    int32_t *d_ids = static_cast<int32_t *>(st.take(4 * (size_t)ndst));
+    uint32_t *d_ut = static_cast<uint32_t *>(st.take(4 * E));
+    uint32_t *d_pc = static_cast<uint32_t *>(st.take(n));
+    uint32_t *d_bt = static_cast<uint32_t *>(st.take(n));
+    int32_t *d_nh = nh ? static_cast<int32_t *>(st.take(n)) : nullptr;
+    int32_t *d_np = nh ? static_cast<int32_t *>(st.take(n)) : nullptr;
+    SDNR_HIP(hipMemcpyAsync(d_ids, dst, 4 * (size_t)ndst, hipMemcpyHostToDevice, ctx->stream));
+    if (E) SDNR_HIP(hipMemcpyAsync(d_ut, util, 4 * E, hipMemcpyHostToDevice, ctx->stream));
+    SDNR_HIP(hipMemcpyAsync(d_pc, pcost, n, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = sdnr_launch_widest_tables(ctx, d_pc, d_ut, d_ids, ndst, d_bt, d_nh, d_np))) return rc;
+    SDNR_HIP(hipMemcpyAsync(bott, d_bt, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (nh) {
+        SDNR_HIP(hipMemcpyAsync(nh, d_nh, n, hipMemcpyDeviceToHost, ctx->stream));
+        SDNR_HIP(hipMemcpyAsync(nh_port, d_np, n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SDNR_HIP(hipStreamSynchronize(ctx->stream));
+    return sdnr_check_watchdog(ctx);
 }
 
 int sdnr_apsp(sdnr_ctx *ctx, uint16_t *dist, uint32_t flags)

@@ -250,6 +250,17 @@ constexpr int kErrLfa = 131072; // sdnr_lfa_tables: a row with P[d][d] != 0 / a 
 constexpr int kLfaMaxV = 16384;
 constexpr int kErrWhatifLoads = 262144; // sdnr_whatif_ecmp_link_loads: a bad override list / bad offsets / sweeps past V / a bad capacity
 
+constexpr int kErrWidest = 524288; // sdnr_widest_tables: a row with pcost[d] != 0 / a vertex of finite cost > 0 without a tight route / sweeps past V
+
+// sdnr_widest_tables keeps pcost and bott of a batch of destinations in LDS:
+// 6 of them (48 bytes per vertex) up to kWidestLdsMaxV6 vertices, 4 (32 bytes)
+// up to kWidestLdsMaxV4, 2 (16 bytes) up to kWidestLdsMaxV -- 159,984 or
+// 160,000 of the CU's 163,840 bytes at the caps --, else 4 in global scratch
+// (32 bytes per vertex and workgroup, at most kLoadsScratchBytes in all)
+constexpr int kWidestLdsMaxV6 = 3333;
+constexpr int kWidestLdsMaxV4 = 5000;
+constexpr int kWidestLdsMaxV = 10000;
+
 // error plumbing (capi.hip)
 int sdnr_fail(int code, const char *fmt, ...);
 int sdnr_hip_fail(hipError_t e, const char *what);
@@ -356,5 +367,9 @@ int sdnr_launch_whatif_peak(sdnr_ctx *ctx, int32_t nscen, const double *d_load,
 int sdnr_launch_lfa_tables(sdnr_ctx *ctx, const uint32_t *d_pcost_all, const int32_t *d_dst,
                            int32_t ndst, int32_t *d_backup, int32_t *d_backup_port,
                            uint8_t *d_kind, uint32_t *d_counts, bool link_only);
+// least-loaded (min-max utilisation) next hops inside the least-cost DAG (widest_tables.hip)
+int sdnr_launch_widest_tables(sdnr_ctx *ctx, const uint32_t *d_pcost, const uint32_t *d_util,
+                              const int32_t *d_dst, int32_t ndst, uint32_t *d_bott, int32_t *d_nh,
+                              int32_t *d_nh_port);
 int sdnr_launch_edge_ports(sdnr_ctx *ctx, const uint64_t *d_ends, int32_t nends,
                            const uint64_t *d_ports, int32_t nports, uint8_t *d_is_edge);

@@ -32,6 +32,7 @@ UNREACHED = -1
 DIST_INF = 0xFFFF
 TREE_NONE = 0xFFFFFFFF
 COST_INF = 0xFFFFFFFF    # sdnr_cost_tables: no route
+UTIL_MAX = 0xFFFFFFFE    # sdnr_widest_tables: the largest link utilisation
 TREE_INT32 = 0           # int32 parents (sdnr_dfs_rows_affected)
 TREE_PORT16 = 1          # parent | port << 16 (sdnr_dfs_tables_packed)
 TREE_SLOT = 2            # parent | slot << 26 (sdnr_dfs_tables_slots)
@@ -51,6 +52,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_cost_ecmp_link_loads", "sdnr_graph_twin_reps", "sdnr_last_dfs_searched",
     "sdnr_last_dfs_form",
     "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables", "sdnr_whatif_ecmp_link_loads",
+    "sdnr_widest_tables",
 )
 
 
@@ -116,6 +118,7 @@ def _bind(L):
         "sdnr_lfa_tables": ([vp, vp, vp, i32, vp, vp, vp, vp, u32], c_int),
         "sdnr_whatif_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp,
                                          vp, vp, u32], c_int),
+        "sdnr_widest_tables": ([vp, vp, vp, vp, i32, vp, vp, vp, u32], c_int),
         "sdnr_graph_twin_reps": ([vp, vp], c_int),
         "sdnr_last_dfs_searched": ([vp, ctypes.POINTER(i32)], c_int),
         "sdnr_last_dfs_form": ([vp, ctypes.POINTER(i32)], c_int),
@@ -354,6 +357,25 @@ class Context(object):
         _check(self._lib.sdnr_cost_tables(self._h, _ptr(dsts), D, _ptr(pcost), _ptr(nh),
                                           _ptr(nhp), 0))
         return pcost, nh, nhp
+
+    def widest_tables(self, pcost, util, dsts, with_nexthop=True):
+        """Least-loaded tables inside the least-cost DAG: (bott uint32 [D, V],
+        nh, nh_port int32 or None) from the pcost rows of ``dsts`` (uint32
+        [D, V], cost_tables') and the link utilisations ``util`` (uint32 [E],
+        CSR edge order), see sdnr_widest_tables."""
+        dsts = np.ascontiguousarray(dsts, np.int32)
+        D, V = int(dsts.shape[0]), self.V
+        pcost = np.ascontiguousarray(pcost, np.uint32)
+        util = np.ascontiguousarray(util, np.uint32)
+        if pcost.shape != (D, V) or util.shape != (self.E,):
+            raise ValueError("pcost is [len(dsts), V] (%d, %d), util one word per link (%d)"
+                             % (D, V, self.E))
+        bott = np.empty((D, V), np.uint32)
+        nh = np.empty((D, V), np.int32) if with_nexthop else None
+        nhp = np.empty((D, V), np.int32) if with_nexthop else None
+        _check(self._lib.sdnr_widest_tables(self._h, _ptr(pcost), _ptr(util), _ptr(dsts), D,
+                                            _ptr(bott), _ptr(nh), _ptr(nhp), 0))
+        return bott, nh, nhp
 
     def expand_routes(self, parent, port, hops, rows, dsts, last_port):
         """Flow entries of many pairs from host tables: (offsets int64
@@ -632,6 +654,17 @@ class Context(object):
             self._h, ctypes.c_void_p(dst_ptr), int(ndst), ctypes.c_void_p(pcost_ptr),
             ctypes.c_void_p(nh_ptr) if nh_ptr else None,
             ctypes.c_void_p(nh_port_ptr) if nh_port_ptr else None, flags))
+
+    def widest_tables_device(self, pcost_ptr, util_ptr, dst_ptr, ndst, bott_ptr, nh_ptr=0,
+                             nh_port_ptr=0, timing=False):
+        """sdnr_widest_tables over device buffers (pcost, bott u32, nh /
+        nh_port int32 [ndst][V]; util u32 [E]; both next-hop pointers or
+        neither), asynchronous."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0)
+        p = lambda a: ctypes.c_void_p(a) if a else None    # noqa: E731
+        _check(self._lib.sdnr_widest_tables(
+            self._h, p(pcost_ptr), p(util_ptr), p(dst_ptr), int(ndst), p(bott_ptr), p(nh_ptr),
+            p(nh_port_ptr), flags))
 
     def apsp_device(self, dist_ptr, timing=False):
         flags = DEVICE_PTRS | (TIMING if timing else 0)

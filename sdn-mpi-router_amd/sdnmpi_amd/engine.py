@@ -47,7 +47,8 @@ __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "COST_ECMP_LDS_MAX_V", "FAILURE_LDS_MAX_V", "normalise_scenarios",
            "failure_ecmp_link_loads_host", "normalise_cost_scenarios",
            "whatif_ecmp_link_loads_host", "peak_utilisation", "lfa_tables_host", "LFA_MAX_V", "LFA_BACKUP",
-           "LFA_DOWNSTREAM", "LFA_NODE"]
+           "LFA_DOWNSTREAM", "LFA_NODE", "widest_tables_host", "check_link_utilisation", "UTIL_MAX",
+           "WIDEST_LDS_MAX_V", "WIDEST_LDS_B4_MAX_V", "WIDEST_LDS_B6_MAX_V"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -480,6 +481,89 @@ def cost_tables_host(csr, cost, dsts):
             nh[i, x] = col[e[first]]
             nhp[i, x] = port[e[first]]
     return pcost, nh, nhp
+
+
+UTIL_MAX = _native.UTIL_MAX     # the largest link utilisation sdnr_widest_tables takes
+WIDEST_LDS_MAX_V = 10000        # csrc/common.h kWidestLdsMaxV: pcost + bott records in LDS up to this V
+WIDEST_LDS_B4_MAX_V = 5000      # ... kWidestLdsMaxV4: in batches of 4 destinations up to this V
+WIDEST_LDS_B6_MAX_V = 3333      # ... kWidestLdsMaxV6: in batches of 6 destinations up to this V
+
+
+def check_link_utilisation(csr, util):
+    """The link utilisations as uint32 [E], after sdnr_widest_tables' checks:
+    one per link, integers in [0, UTIL_MAX]."""
+    u = np.asarray(util)
+    if u.shape != (int(csr.E),):
+        raise ValueError("one utilisation per link of the graph (%d)" % int(csr.E))
+    if u.size:
+        if u.dtype.kind not in "iu":
+            raise ValueError("link utilisations are integers")
+        if int(u.min()) < 0 or int(u.max()) > UTIL_MAX:
+            raise ValueError("link utilisations are in [0, 2**32 - 2]")
+    return u.astype(np.uint32)
+
+
+def widest_tables_host(csr, cost, pcost, util, dsts):
+    """numpy / Python restatement of sdnr_widest_tables (the CPU tests' engine
+    double and the checker of widest_tables.hip): (bott uint32 [D, V], nh
+    int32, nh_port int32) -- per destination of ``dsts`` the least-loaded
+    route inside the least-cost DAG.
+
+    ``cost``: uint32 [E] link costs (None: every link costs 1); ``pcost``:
+    [D, V] u32 (or int32 holding u32) rows of the least costs toward
+    ``dsts[i]`` under them; ``util``: uint32 [E] link utilisations.  Link e =
+    (x -> n) is tight when pcost[n] is finite and pcost[n] + cost[e] ==
+    pcost[x]; bott[x] = min over tight e of max(util[e], bott[n]), 0 at the
+    destination, COST_INF where there is no route; nh[x] the tight link of the
+    smallest (max(util[e], bott[n]), util[e], n).  A destination outside
+    [0, V) gives an empty row.
+
+    Deliberately not the kernel's algorithm: the vertices of a row are
+    processed once, in ascending pcost order -- a tight link leads to a
+    strictly cheaper vertex, which is final by then -- with Python ints and
+    tuple comparison for the key."""
+    V, E = int(csr.V), int(csr.E)
+    cost = np.ones(E, np.uint32) if cost is None else check_link_costs(csr, cost)
+    util = check_link_utilisation(csr, util)
+    P = _pcost_u32(pcost)
+    dsts = np.asarray(dsts, np.int64)
+    D = int(dsts.shape[0])
+    if P.shape != (D, V):
+        raise ValueError("pcost holds one [V] row per destination")
+    bott = np.full((D, V), COST_INF, np.uint32)
+    nh = np.full((D, V), -1, np.int32)
+    nhp = np.full((D, V), -1, np.int32)
+    rp = np.asarray(csr.row_ptr, np.int64).tolist()
+    col = np.asarray(csr.col, np.int64).tolist()
+    port = np.asarray(csr.port, np.int64).tolist()
+    c, u = cost.tolist(), util.tolist()
+    INF = int(COST_INF)
+    for i, d in enumerate(dsts.tolist()):
+        if d < 0 or d >= V:
+            continue                                       # unknown destination: empty row
+        pc = P[i].astype(np.int64).tolist()
+        if pc[d] != 0:
+            raise ValueError("pcost row %d is not a least-cost row of destination %d" % (i, d))
+        b = [INF] * V
+        b[d] = 0
+        for x in sorted((x for x in range(V) if pc[x] != INF and x != d), key=pc.__getitem__):
+            best = None
+            for e in range(rp[x], rp[x + 1]):
+                n = col[e]
+                if pc[n] != INF and pc[n] + c[e] == pc[x] and b[n] != INF:
+                    key = (max(u[e], b[n]), u[e], n)
+                    if best is None or key < best[0]:
+                        best = (key, e)
+            if best is None:
+                if pc[x] != 0:
+                    raise ValueError("vertex %d of row %d has finite cost and no tight link"
+                                     % (x, i))
+                continue
+            b[x] = best[0][0]
+            nh[i, x] = col[best[1]]
+            nhp[i, x] = port[best[1]]
+        bott[i] = np.asarray(b, np.uint32)
+    return bott, nh, nhp
 
 
 COST_ECMP_LDS_MAX_V = 7400      # csrc/common.h kCostEcmpLdsMaxV: ECMP-under-costs row state in LDS
@@ -1484,6 +1568,51 @@ class RouteEngine(object):
                                        link_only=link_only, timing=timing)
             self.ctx.synchronize()          # raises on a row that is no least-cost labelling
         return backup, bport, kind, counts.cpu().numpy().view(np.uint32)
+
+    def widest_tables(self, export, cost, pcost, util, dsts, timing=False):
+        """Least-loaded tables inside the least-cost DAG (widest_tables.hip,
+        sdnr_widest_tables): (bott int32 [D, V] holding u32 -- -1 is
+        0xFFFFFFFF, no route --, nh, nh_port int32) on the device, as
+        ``cost_tables`` returns its tables and as ``widest_tables_host``
+        defines them.
+
+        ``cost``: uint32 [E] link costs, or None for unit costs (the context's
+        costs are then cleared); ``pcost``: the [D, V] least-cost rows of
+        ``dsts`` under those costs -- a device tensor (int32 holding u32, as
+        ``cost_tables`` returns it) or a numpy array, which is uploaded;
+        ``util``: uint32 [E] link utilisations in [0, UTIL_MAX].  A destination
+        outside [0, V) gives an empty row."""
+        if cost is None:
+            self.load(export)
+            if self._costs is not None:
+                self._costs = None
+                self.ctx.set_link_costs(None)
+        else:
+            self.set_link_costs(export, cost)
+        t = self._torch
+        V = int(export.csr.V)
+        util = check_link_utilisation(export.csr, util)
+        d = np.asarray(dsts, np.int64)
+        D = int(d.shape[0])
+        d = np.where((d < 0) | (d >= V), -1, d).astype(np.int32)
+        if _is_np(pcost):
+            pcost = t.from_numpy(np.ascontiguousarray(_pcost_u32(pcost)).view(np.int32)
+                                 ).to(self.dev)
+        if tuple(pcost.shape) != (D, V) or pcost.element_size() != 4:
+            raise ValueError("pcost holds one 4-byte [V] row per destination")
+        pcost = pcost.contiguous()
+        bott = self._empty(D, V, t.int32)
+        nh = self._empty(D, V, t.int32)
+        nhp = self._empty(D, V, t.int32)
+        if D and V:
+            td = t.from_numpy(d).to(self.dev)
+            tu = t.from_numpy(util.view(np.int32)).to(self.dev)
+            self._ready()
+            self.ctx.widest_tables_device(pcost.data_ptr(), tu.data_ptr(), td.data_ptr(), D,
+                                          bott.data_ptr(), nh.data_ptr(), nhp.data_ptr(),
+                                          timing=timing)
+            self.ctx.synchronize()          # raises on a row that is no least-cost labelling
+        return bott, nh, nhp
 
     def edge_ports(self, ends, ports):
         """Flood-port mask (sdnr_edge_ports, reference topology.py:150-155):

@@ -26,7 +26,7 @@ first route query raises (``sdnmpi_amd._native.NativeUnavailable`` /
 
 import numpy as np
 
-from ..engine import (COST_INF, COST_MAX, DEFAULT_TABLE_BUDGET, INT32, LFA_MAX_V, RouteEngine, TableCache, _gather,
+from ..engine import (COST_INF, COST_MAX, DEFAULT_TABLE_BUDGET, INT32, LFA_MAX_V, UTIL_MAX, RouteEngine, TableCache, _gather,
                       _host, _take, _torch, _u16, check_link_costs, least_cost_paths_lex,
                       peak_utilisation,
                       shortest_paths_lex, tree_path)
@@ -39,7 +39,7 @@ except Exception:   # noqa: BLE001 - Ryu is not a dependency of the engine
     OFPP_LOCAL = 0xfffe
 
 __all__ = ["TopologyDB", "LinkLoads", "SplitLinkLoads", "FailureLoads", "CostChangeLoads",
-           "CostTuning", "OFPP_LOCAL",
+           "CostTuning", "Admission", "OFPP_LOCAL",
            "sdn_mpi_mac"]
 
 _INF = 0xFFFF
@@ -205,6 +205,35 @@ class CostTuning(object):
         self.history = history
 
 
+class Admission(object):
+    """Result of :meth:`TopologyDB.admit_flows`: what the links carry once the
+    flows were admitted in order, each slice on its least-loaded routes.
+
+    ``loads``: :class:`LinkLoads` of the admitted traffic (exact uint64).
+    ``peak_before`` / ``peak_link_before``: the largest per-link figure -- the
+    load, or ``load * 1024 // capacity`` where capacities were given, a Python
+    int -- and the first link ``(src_dpid, dst_dpid)`` that attains it (None
+    on a fabric without links) when every pair takes the lexicographic
+    least-cost route instead (:meth:`TopologyDB.least_cost_link_loads`);
+    ``peak_after`` / ``peak_link_after``: the same of ``loads``.  ``lost``:
+    the weight of the known pairs that have no route.  ``rounds``: the slices
+    the pairs were admitted in.  ``routes``: with ``routes=True`` the fdb of
+    every pair, in ``find_route``'s format ([] where there is none), else
+    None."""
+
+    def __init__(self, loads, peak_before, peak_link_before, peak_after, peak_link_after, lost,
+                 rounds, routes):
+        self.loads = loads
+        self.peak_before, self.peak_link_before = peak_before, peak_link_before
+        self.peak_after, self.peak_link_after = peak_after, peak_link_after
+        self.lost = lost
+        self.rounds = rounds
+        self.routes = routes
+
+
+CAPACITY_MAX = 1 << 53            # admit_flows: load * 1024 // capacity stays in 64 bits
+
+
 def _weights(weights, n):
     """u64 weights of n pairs (None: ones); negative or oversized: ValueError."""
     if weights is None:
@@ -251,6 +280,10 @@ class TopologyDB(object):
         self._cost_version = 0
         self._cost_vec = None            # (export, cost version, uint32 [E] costs)
         self._cost_memo = None           # least-cost rows per destination (_cost_rows)
+        self._link_utils = {}            # (src dpid, dst dpid) -> utilisation (monitor data)
+        self._util_version = 0
+        self._util_vec = None            # (export, utilisation version, uint32 [E])
+        self._util_memo = None           # least-loaded rows per destination (_widest_rows)
         # Switch DPID -> Switch; src DPID -> dst DPID -> Link; MAC -> Host
         self.switches = {}
         self.links = {}
@@ -1281,6 +1314,390 @@ class TopologyDB(object):
         :meth:`mpi_link_loads`)."""
         pairs, weights = self._rank_pairs(rank_to_mac, traffic)
         return self.least_cost_link_loads(pairs, weights)
+
+    # -- link utilisation and least-loaded routes ---------------------------
+    def set_link_utilisation(self, src_dpid, dst_dpid, value):
+        """Utilisation of the directed link src_dpid -> dst_dpid for the
+        least-loaded routes (what the port counters measured, in any unit;
+        default 0): an int in [0, 2**32 - 2], else ValueError.  Monitor data,
+        kept by dpid pair independently of ``links`` as the costs are: it
+        applies whenever that link exists, so a flapping link keeps its
+        figure.  Only the ``least_loaded`` methods and ``admit_flows`` read
+        it."""
+        self.set_link_utilisations({(src_dpid, dst_dpid): value})
+
+    @staticmethod
+    def _checked_utilisations(mapping, what):
+        items = list(dict(mapping).items())
+        for k, x in items:
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or \
+                    not 0 <= int(x) <= UTIL_MAX:
+                raise ValueError("link utilisation of %r must be an int in [0, 2**32 - 2]: %r"
+                                 % (k, x))
+            if not isinstance(k, tuple) or len(k) != 2:
+                raise ValueError("link utilisations are keyed by %s: %r" % (what, k))
+        return items
+
+    def set_link_utilisations(self, mapping):
+        """:meth:`set_link_utilisation` for every {(src_dpid, dst_dpid):
+        value} of ``mapping``; nothing is set when one of them is refused."""
+        for k, x in self._checked_utilisations(mapping, "(src_dpid, dst_dpid)"):
+            self._link_utils[(k[0], k[1])] = int(x)
+        self._util_version += 1
+
+    def set_port_utilisations(self, mapping):
+        """:meth:`set_link_utilisations` keyed as the Monitor keys its port
+        statistics: {(dpid, port_no): value}, resolved to the link whose
+        source port it is (``links[dpid][*].src.port_no``).  Ports that are no
+        link's source (host ports, unknown switches) are ignored; nothing is
+        set when one value is refused."""
+        items = self._checked_utilisations(mapping, "(dpid, port_no)")
+        by_port = {(a, lk.src.port_no): (a, b) for a, nb in self.links.items()
+                   for b, lk in nb.items()}
+        self.set_link_utilisations({by_port[k]: x for k, x in items if k in by_port})
+
+    def link_utilisation(self, src_dpid, dst_dpid):
+        """The utilisation set for src_dpid -> dst_dpid (0 when none was)."""
+        return self._link_utils.get((src_dpid, dst_dpid), 0)
+
+    def clear_link_utilisations(self):
+        """Every link back to utilisation 0."""
+        self._link_utils.clear()
+        self._util_version += 1
+
+    def _util_vector(self, ex):
+        """uint32 [E]: the utilisation of every link of the export, CSR edge order."""
+        got = self._util_vec
+        if got is not None and got[0] is ex and got[1] == self._util_version:
+            return got[2]
+        util = np.zeros(int(ex.csr.E), np.uint32)
+        for (a, b), x in self._link_utils.items():
+            e = self._link_edge(ex, a, b)
+            if e is not None:
+                util[e] = x
+        self._util_vec = (ex, self._util_version, util)
+        return util
+
+    def _widest_cap(self, ex):
+        """Destinations per engine call: the least-cost rows and the
+        least-loaded rows of a chunk (12 bytes per vertex each) fit the table
+        budget together."""
+        budget = DEFAULT_TABLE_BUDGET if self._budget is None else self._budget
+        return max(1, int(budget) // max(1, 24 * int(ex.csr.V)))
+
+    def _widest_compute(self, ex, dsts, util):
+        """(bott, nh, nh_port) [n, V] as the engine returns them -- bott held
+        as int32, -1: no route -- of the distinct destinations ``dsts`` (at
+        most :meth:`_widest_cap`) under the utilisation vector ``util``; the
+        least-cost rows come from the least-cost memo."""
+        m = self._cost_rows(ex, dsts)
+        idx = np.asarray([m["slot"][d] for d in dsts], np.int64)
+        tabs = tuple(self.engine.widest_tables(ex, self._cost_vector(ex), _take(m["tabs"][0], idx),
+                                               util, dsts))
+        if isinstance(tabs[0], np.ndarray):
+            tabs = (np.ascontiguousarray(tabs[0], np.uint32).view(np.int32),) + tabs[1:]
+        return tabs
+
+    def _widest_rows(self, ex, want):
+        """Memo of least-loaded rows holding every destination of ``want`` (at
+        most :meth:`_widest_cap` of them), in :meth:`_cost_rows`' form: kept
+        until the graph, the costs or the utilisation change, or the table
+        budget is exceeded."""
+        m = self._util_memo
+        key = (self._cost_version, self._util_version)
+        if m is None or m["ex"] is not ex or m["version"] != key:
+            m = self._util_memo = {"ex": ex, "version": key, "slot": {}, "tabs": None}
+        new = [d for d in want if d not in m["slot"]]
+        if not new:
+            return m
+        if len(m["slot"]) + len(new) > self._widest_cap(ex):
+            m["slot"], m["tabs"] = {}, None
+            new = list(want)
+        tabs = self._widest_compute(ex, new, self._util_vector(ex))
+        base = len(m["slot"])
+        if m["tabs"] is None:
+            m["tabs"] = tabs
+        elif isinstance(tabs[0], np.ndarray):
+            m["tabs"] = tuple(np.concatenate([a, b]) for a, b in zip(m["tabs"], tabs))
+        else:
+            m["tabs"] = tuple(_torch().cat([a, b]) for a, b in zip(m["tabs"], tabs))
+        for k, d in enumerate(new):
+            m["slot"][d] = base + k
+        return m
+
+    def least_loaded_tables(self, vertices=None):
+        """Per-destination tables of the least-loaded routes (widest_tables
+        .hip): inside the least-cost routes under the link costs, the route
+        whose busiest link has the smallest utilisation (:meth:`set_link_
+        utilisation`), for every host-bearing switch or the dense ``vertices``
+        given: dict(destinations, bott uint32 [n, V] -- the utilisation of
+        that busiest link, 0xFFFFFFFF where there is no route --, nh, nh_port
+        int32, dpids).  ``nh`` is the tight link of the smallest (bottleneck,
+        utilisation of the link itself, neighbour); with no utilisation set
+        the tables are :meth:`least_cost_tables`'."""
+        ex = self.graph()
+        hv = self._host_vertices(ex) if vertices is None else [int(v) for v in vertices]
+        V, n = int(ex.csr.V), len(hv)
+        bott = np.empty((n, V), np.uint32)
+        nh = np.empty((n, V), np.int32)
+        nhp = np.empty((n, V), np.int32)
+        step = self._widest_cap(ex)
+        for i in range(0, n, step):                 # a budget's worth of rows at a time
+            chunk = hv[i:i + step]
+            m = self._widest_rows(ex, sorted(set(chunk)))
+            idx = np.asarray([m["slot"][v] for v in chunk], np.int64)
+            b, a, p = (_host(_take(t, idx)) for t in m["tabs"])
+            bott[i:i + len(chunk)] = b.view(np.uint32)
+            nh[i:i + len(chunk)] = a
+            nhp[i:i + len(chunk)] = p
+        return {"destinations": np.asarray(hv, np.int32), "bott": bott, "nh": nh,
+                "nh_port": nhp, "dpids": ex.csr.dpids}
+
+    def find_route_least_loaded(self, src_mac, dst_mac):
+        """The least-loaded route between two hosts (or switch-local ports):
+        of the least-cost routes the one whose busiest link is the least
+        utilised, in ``find_route``'s format and with its endpoint rules.
+        Always one of ``find_route_least_cost(..., multiple=True)``, and
+        ``find_route_least_cost(...)`` itself while no utilisation is set."""
+        return self.find_routes_least_loaded([(src_mac, dst_mac)])[0]
+
+    def find_routes_least_loaded(self, pairs):
+        """:meth:`find_route_least_loaded` over many (src_mac, dst_mac) pairs;
+        the destination rows are computed once for all of them."""
+        pairs = list(pairs)
+        ex = self.graph()
+        out = [[] for _ in pairs]
+        ends = {}
+        for i, (a, b) in enumerate(pairs):
+            ea, eb = self._endpoint(a), self._endpoint(b)
+            if ea is None or eb is None:
+                continue
+            ends[i] = (ex.index[ea[0]], ex.index[eb[0]], self._last_hop(eb[0], eb[1], b))
+        want = sorted(set(e[1] for e in ends.values()))
+        step = self._widest_cap(ex)
+        for c0 in range(0, len(want), step):        # a budget's worth of rows at a time
+            chunk = want[c0:c0 + step]
+            m = self._widest_rows(ex, chunk)
+            idx = np.asarray([m["slot"][d] for d in chunk], np.int64)
+            host = [_host(_take(t, idx)) for t in m["tabs"]]
+            at = {d: k for k, d in enumerate(chunk)}
+            for i, (s, d, last) in ends.items():
+                if d in at:
+                    k = at[d]
+                    out[i] = self._least_cost_fdb(ex, s, d, last,
+                                                  (host[0][k], host[1][k], host[2][k]))
+        return out
+
+    def _switch_pair_widest_loads(self, ex, sv, dv, w, util=None, rows_out=None):
+        """(load uint64 [E], reach bool [n]) of switch pairs (dense ids sv ->
+        dv, weights w u64) on their least-loaded routes: sdnr_link_loads with
+        SDNR_LOADS_TO_ROOT over the least-loaded next-hop rows, a budget-sized
+        chunk of destination rows at a time.  ``util``: a utilisation vector
+        in place of the one set (its rows are not memoised); ``rows_out``: a
+        dict that receives {destination: (bott, nh, nh_port) host rows}."""
+        E = int(ex.csr.E)
+        load = np.zeros(E, np.uint64)
+        reach = np.zeros(sv.shape[0], bool)
+        if sv.size == 0:
+            return load, reach
+        want = sorted(set(dv.tolist()))
+        step = self._widest_cap(ex)
+        for c0 in range(0, len(want), step):
+            chunk = want[c0:c0 + step]
+            if util is None:
+                m = self._widest_rows(ex, chunk)
+                slot, tabs = m["slot"], m["tabs"]
+            else:
+                slot, tabs = {d: k for k, d in enumerate(chunk)}, self._widest_compute(ex, chunk,
+                                                                                       util)
+            mine = np.nonzero(np.isin(dv, np.asarray(chunk, np.int64)))[0]
+            slots = np.asarray([slot[v] for v in dv[mine].tolist()], np.int64)
+            # bott is held as int32: no route reads -1
+            reach[mine] = _gather(tabs[0], slots, sv[mine]) != -1
+            urows, inv = np.unique(slots, return_inverse=True)
+            load += self.engine.link_loads(ex, _take(tabs[1], urows), INT32, inv, sv[mine],
+                                           w[mine], to_root=True)
+            if rows_out is not None:
+                idx = np.asarray([slot[d] for d in chunk], np.int64)
+                host = [_host(_take(t, idx)) for t in tabs]
+                for k, d in enumerate(chunk):
+                    rows_out[d] = (host[0][k], host[1][k], host[2][k])
+        return load, reach
+
+    def least_loaded_link_loads(self, pairs, weights=None):
+        """:meth:`link_loads` with every pair on its least-loaded route
+        (:meth:`find_route_least_loaded`) under the utilisation as set -- what
+        the pairs add to the links if all of them are routed on the tables as
+        they stand: ``as_dict()`` is the weighted count of the ``(dpid,
+        out_port)`` entries of those routes.  Exact uint64 sums."""
+        return self._pair_loads(pairs, weights, self._switch_pair_widest_loads, LinkLoads)
+
+    def mpi_least_loaded_link_loads(self, rank_to_mac, traffic=None):
+        """:meth:`least_loaded_link_loads` of an MPI job (``traffic`` as in
+        :meth:`mpi_link_loads`)."""
+        pairs, weights = self._rank_pairs(rank_to_mac, traffic)
+        return self.least_loaded_link_loads(pairs, weights)
+
+    # -- admission: the flows of a job, routed round by round ---------------
+    def _int_capacity_vector(self, ex, capacity):
+        """uint64 [E] capacities in CSR edge order from one int for every link
+        or ``{(src_dpid, dst_dpid): int}`` (links not named: 1; links that do
+        not exist are ignored), each in [1, 2**53]; None when none is given."""
+        if capacity is None:
+            return None
+
+        def checked(key, x):
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or \
+                    not 1 <= int(x) <= CAPACITY_MAX:
+                raise ValueError("capacity of %r must be an int in [1, 2**53]: %r" % (key, x))
+            return int(x)
+
+        E = int(ex.csr.E)
+        if not hasattr(capacity, "items") and not hasattr(capacity, "__iter__"):
+            return np.full(E, checked("every link", capacity), np.uint64)
+        cap = np.ones(E, np.uint64)
+        for key, x in dict(capacity).items():
+            if not isinstance(key, tuple) or len(key) != 2:
+                raise ValueError("capacities are keyed by (src_dpid, dst_dpid): %r" % (key,))
+            x = checked(key, x)
+            e = self._link_edge(ex, key[0], key[1])
+            if e is not None:
+                cap[e] = x
+        return cap
+
+    @staticmethod
+    def _admission_util(base, admitted, cap):
+        """uint32 [E]: min(base + min(u(admitted), UTIL_MAX), UTIL_MAX) with
+        u(load) = load * 1024 // capacity, or the load itself without
+        capacities -- in 64-bit integers that cannot wrap."""
+        top = np.uint64(UTIL_MAX)
+        if cap is None:
+            a = np.minimum(admitted, top)
+        else:
+            # load = q * cap + r: load * 1024 // cap = q * 1024 + r * 1024 // cap
+            q, r = admitted // cap, admitted % cap
+            a = np.minimum(np.minimum(q, top) * np.uint64(1024) + r * np.uint64(1024) // cap, top)
+        return np.minimum(base.astype(np.uint64) + a, top).astype(np.uint32)
+
+    def _peak(self, ex, load, cap):
+        """(peak, link): the largest load[e] (load[e] * 1024 // capacity[e]
+        with capacities) as a Python int and the first link (src_dpid,
+        dst_dpid) that attains it; (0, None) on a fabric without links."""
+        vals = load.tolist()
+        if cap is not None:
+            vals = [x * 1024 // c for x, c in zip(vals, cap.tolist())]
+        if not vals:
+            return 0, None
+        peak = max(vals)
+        return peak, self._edge_links(ex)(vals.index(peak))
+
+    @staticmethod
+    def _admission_slices(dv, pos, n, batch):
+        """Index arrays into the known pairs, one per round: ``batch`` None --
+        the pairs of one destination switch, the switches in order of first
+        appearance; else the known ones of each ``batch`` consecutive pairs of
+        the list as given (``pos``: the known pairs' positions in it, ``n``
+        its length)."""
+        if batch is None:
+            perm = np.argsort(dv, kind="stable")
+            cut = np.nonzero(np.diff(dv[perm]))[0] + 1
+            groups = [g for g in np.split(perm, cut) if g.size]
+            return sorted(groups, key=lambda g: int(g[0]))
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or int(batch) < 1:
+            raise ValueError("batch is a positive number of pairs per round, or None")
+        cuts = np.searchsorted(pos, np.arange(0, n + int(batch), int(batch)))
+        return [np.arange(a, b) for a, b in zip(cuts[:-1].tolist(), cuts[1:].tolist())]
+
+    def _admit(self, ex, sv, dv, w, slices, cap, rows_out=None):
+        """(admitted load uint64 [E], reach bool per pair) of pairs (dense
+        switches sv -> dv, weights w u64) admitted slice by slice: each slice
+        is routed on the least-loaded tables under the utilisation as set plus
+        what the earlier slices put on the links.  ``rows_out``: a list that
+        receives, per slice, {destination: (bott, nh, nh_port) host rows}."""
+        V = max(1, int(ex.csr.V))
+        base = self._util_vector(ex)
+        admitted = np.zeros(int(ex.csr.E), np.uint64)
+        reach = np.zeros(sv.shape[0], bool)
+        want = sorted(set(dv.tolist()))
+        if 0 < len(want) <= self._cost_cap(ex):
+            self._cost_rows(ex, want)               # the least-cost rows of every round, once
+        for sl in slices:
+            rows = None if rows_out is None else {}
+            if sl.size:
+                # the slice's pairs summed to switch pairs
+                key, inv = np.unique(sv[sl] * V + dv[sl], return_inverse=True)
+                inv = inv.reshape(-1)
+                sw = np.zeros(key.shape[0], np.uint64)
+                np.add.at(sw, inv, w[sl])
+                load, got = self._switch_pair_widest_loads(
+                    ex, key // V, key % V, sw, self._admission_util(base, admitted, cap), rows)
+                admitted += load
+                reach[sl] = got[inv]
+            if rows_out is not None:
+                rows_out.append(rows)
+        return admitted, reach
+
+    def admit_flows(self, pairs, weights=None, capacity=None, batch=None, routes=False):
+        """Admit the flows of ``pairs`` (weights as in :meth:`link_loads`) in
+        order, a slice at a time, every slice on its least-loaded routes under
+        what the links carry by then -- the routes a controller would install
+        if it looked at its port counters before each batch of flows -- and
+        return an :class:`Admission`.
+
+        Slices: ``batch`` consecutive pairs of the list each; by default
+        (``batch=None``) one slice per distinct destination switch, the
+        switches in order of first appearance in ``pairs`` (the pairs of a
+        slice share their destination row, so a round is one row of tables).
+        A slice is routed on the least-loaded tables (:meth:`least_loaded_
+        tables`' rule) under ``util = min(base + u(admitted), 2**32 - 2)``:
+        ``base`` the utilisation as set, ``admitted`` the exact uint64 link
+        loads of the slices before it, and ``u(load) = min(load * 1024 //
+        capacity[e], 2**32 - 2)`` with ``capacity`` -- one int for every link
+        or ``{(src_dpid, dst_dpid): int}``, links not named 1, each in
+        [1, 2**53] -- or ``min(load, 2**32 - 2)`` without.  All in integers.
+        One slice holding everything is :meth:`least_loaded_link_loads`; one
+        pair per slice is greedy sequential admission.
+
+        Every route stays least-cost, so the total carried load equals that of
+        :meth:`least_cost_link_loads`; only the peak moves.  Nothing of this
+        object changes: not ``links``, the costs, the utilisation as set, the
+        least-loaded tables or the graph on the GPU.  Only the destination
+        rows a slice needs are computed for it (widest_tables.hip, then the
+        loads kernel over its next-hop rows)."""
+        pairs = list(pairs)
+        weights = None if weights is None else list(weights)
+        ex = self.graph()
+        cap = self._int_capacity_vector(ex, capacity)
+        w, dv, last, ok, inv, ssv, sdv, _ = self._switch_pairs(ex, pairs, weights)
+        sv_ok, dv_ok, w_ok = ssv[inv.reshape(-1)], sdv[inv.reshape(-1)], w[ok]
+        slices = self._admission_slices(dv_ok, ok, len(pairs), batch)
+        rows = [] if routes else None
+        load, reach = self._admit(ex, sv_ok, dv_ok, w_ok, slices, cap, rows)
+        got = ok[reach]
+        hkey, hinv = np.unique(np.stack([dv[got], last[got]], 1), axis=0, return_inverse=True)
+        hload = np.zeros(hkey.shape[0], np.uint64)
+        np.add.at(hload, hinv.reshape(-1), w[got])
+        fdbs = None
+        if routes:
+            fdbs = [[] for _ in pairs]
+            for sl, tabs in zip(slices, rows):
+                for k in sl.tolist():
+                    i, d = int(ok[k]), int(dv_ok[k])
+                    b = pairs[i][1]
+                    eb = self._endpoint(b)
+                    fdbs[i] = self._least_cost_fdb(ex, int(sv_ok[k]), d,
+                                                   self._last_hop(eb[0], eb[1], b), tabs[d])
+        before = self.least_cost_link_loads(pairs, weights)
+        pb, lb = self._peak(ex, before.load, cap)
+        pa, la = self._peak(ex, load, cap)
+        return Admission(self._link_loads_result(ex, load, hkey.reshape(-1, 2), hload), pb, lb,
+                         pa, la, int(w_ok[~reach].sum(dtype=np.uint64)), len(slices), fdbs)
+
+    def mpi_admit_flows(self, rank_to_mac, traffic=None, capacity=None, batch=None, routes=False):
+        """:meth:`admit_flows` of an MPI job (``traffic`` as in
+        :meth:`mpi_link_loads`)."""
+        pairs, weights = self._rank_pairs(rank_to_mac, traffic)
+        return self.admit_flows(pairs, weights, capacity, batch, routes)
 
     # -- ECMP over the least-cost routes ----------------------------------
     def _switch_pair_cost_ecmp_loads(self, ex, sv, dv, w, split):
