@@ -14,7 +14,9 @@ tree ``parent_s`` (the tree of first pushes):
 
 * removed link (u, v), or a new port on it: the search looks at (u, v) only
   when it pops u, and pushes v only if v is unvisited then -- which is exactly
-  ``parent_s[v] == u``.  Any other row is unchanged.
+  ``parent_s[v] == u`` with ``v != s`` (the root's entry ``parent_s[s] == s``
+  stands for no link: a self-loop (s, s) is looked at when s, visited, is
+  popped, and never taken).  Any other row is unchanged.
 * added link (u, v): it matters iff u is reached and v is still unvisited
   when u is popped: v unreached, or v pushed (by ``parent_s[v]``) in a pop
   that comes after u's.  Pops follow the tree's preorder with children taken
@@ -192,13 +194,15 @@ def dfs_rows_affected(parent, hops, srcs, diff):
     xp = _ns(parent)
     S = parent.shape[0]
     out = xp.zeros_bool(S)
+    srcs = xp.i64(np.asarray(srcs, np.int64))
     # removed or re-ported link (u, v): only when it is the tree edge into v
+    # (the root's own entry is no tree edge: parent_s[s] == s, and a self-loop
+    # link (s, s) is never taken)
     for u, v in (diff.removed, diff.ported):
         for uu, vv in zip(u.tolist(), v.tolist()):
-            out |= parent[:, vv] == uu
+            out |= (parent[:, vv] == uu) & (srcs != vv)
     # added link (u, v)
     rows_all = xp.i64(np.arange(S, dtype=np.int64))
-    srcs = xp.i64(np.asarray(srcs, np.int64))
     for uu, vv in zip(diff.added[0].tolist(), diff.added[1].tolist()):
         if uu == vv:
             continue                                  # u is visited when popped

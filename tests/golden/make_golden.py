@@ -84,6 +84,31 @@ def fabric_arrays(f):
                 host_port=f.host_port, switches=f.switches)
 
 
+LOOP_PORTS = (70, 71)        # both ends of an added self-loop link
+
+
+def with_self_loops(fabric, seed):
+    """The fabric plus a link (u:70 -> u:71) on a seeded third of its switches
+    (every dpid the CSR knows), appended after the fabric's own links."""
+    dpids = [int(d) for d in fabric.csr().dpids]
+    rng = random.Random(seed)
+    loops = sorted(rng.sample(dpids, max(1, (len(dpids) + 2) // 3)))
+    n = len(loops)
+    cat = lambda a, b: np.concatenate([a, np.asarray(b, np.int64)])  # noqa: E731
+    return T.Fabric(fabric.name + "_loops",
+                    cat(fabric.link_src, loops), cat(fabric.link_sport, [LOOP_PORTS[0]] * n),
+                    cat(fabric.link_dst, loops), cat(fabric.link_dport, [LOOP_PORTS[1]] * n),
+                    fabric.host_mac, fabric.host_dpid, fabric.host_port, fabric.switches,
+                    dict(fabric.params, loops=loops))
+
+
+def without_self_loops(fabric):
+    keep = fabric.link_src != fabric.link_dst
+    return T.Fabric(fabric.name, fabric.link_src[keep], fabric.link_sport[keep],
+                    fabric.link_dst[keep], fabric.link_dport[keep], fabric.host_mac,
+                    fabric.host_dpid, fabric.host_port, fabric.switches)
+
+
 def run_fabric(TopologyDB, name, fabric, pairs=None, multiple=False,
                store_fabric=True, n_sample=None, seed=0):
     t0 = time.time()
@@ -104,6 +129,14 @@ def run_fabric(TopologyDB, name, fabric, pairs=None, multiple=False,
         mres = [db.find_route(macs[a], macs[b], True) for a, b in pairs]
         (out["m_pair_off"], out["m_route_off"], out["m_dpid"],
          out["m_port"]) = flatten_multi(mres)
+    if name.endswith("_loops"):
+        # inertness, pinned by the reference itself: the same fabric without
+        # its self-loop links answers every query the same way
+        assert (fabric.link_src == fabric.link_dst).any(), name
+        bare = without_self_loops(fabric).populate(TopologyDB())
+        assert res == [bare.find_route(macs[a], macs[b]) for a, b in pairs], name
+        if multiple:
+            assert mres == [bare.find_route(macs[a], macs[b], True) for a, b in pairs], name
     csr = fabric.csr()
     out["csr_digest"] = np.array(csr.digest())
     out["V"], out["E"] = np.int64(csr.V), np.int64(csr.E)
@@ -241,10 +274,14 @@ def main():
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--large-only", action="store_true",
                     help="regenerate only the full-size samples")
+    ap.add_argument("--loops-only", action="store_true",
+                    help="regenerate only the self-loop fixtures")
     args = ap.parse_args()
     TopologyDB = import_reference()
     if args.large_only:
         return large(TopologyDB)
+    if args.loops_only:
+        return loops(TopologyDB)
 
     scenarios(TopologyDB)
     run_fabric(TopologyDB, "mock", T.mock_square(), multiple=True)
@@ -262,9 +299,24 @@ def main():
     run_fabric(TopologyDB, "random_V12", random_directed(12, 30, 9, seed=4,
                                                          dpid_spread=False),
                multiple=True)
+    loops(TopologyDB)
     if args.small:
         return
     large(TopologyDB)
+
+
+def loops(TopologyDB):
+    # the same fabrics with self-loop links (a cable between two ports of one
+    # switch); run_fabric asserts that the reference answers as without them
+    run_fabric(TopologyDB, "fat_tree_k4_loops", with_self_loops(T.fat_tree(4), 41),
+               multiple=True)
+    run_fabric(TopologyDB, "torus_2x2x2_loops", with_self_loops(T.torus3d(2, 2, 2), 42),
+               multiple=True)
+    run_fabric(TopologyDB, "random_V12_loops",
+               with_self_loops(random_directed(12, 30, 9, seed=4, dpid_spread=False), 43),
+               multiple=True)
+    run_fabric(TopologyDB, "random_V40_loops",
+               with_self_loops(random_directed(40, 110, 30, seed=11), 44))
 
 
 def large(TopologyDB):

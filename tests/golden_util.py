@@ -13,6 +13,11 @@ SMALL = ["mock", "fat_tree_k4", "fat_tree_k8", "torus_4x4x4", "torus_2x2x2",
          "torus_5x3x2", "dragonfly_a4_h2_p2", "jellyfish_n60_r5", "random_V40",
          "random_V60_dense", "random_V9", "random_V12"]
 MULTI = ["mock", "fat_tree_k4", "torus_2x2x2", "random_V9", "random_V12"]
+# the same fabrics with a self-loop link (u:70 -> u:71) on a third of the
+# switches; the reference answers as without them (make_golden.run_fabric)
+LOOPS = ["fat_tree_k4_loops", "torus_2x2x2_loops", "random_V12_loops", "random_V40_loops"]
+SMALL += LOOPS
+MULTI += LOOPS[:3]
 # full-size BASELINE configs (sampled pairs) and their canonical generators
 LARGE = {
     "fat_tree_k48_sample": lambda: T.fat_tree(48),

@@ -58,6 +58,38 @@ def step_event(db, rng, dpids, nxt):
     return "cost_clear"
 
 
+LOOP_KINDS = ("loop_delete", "loop_report", "loop_cost", "loop_add")
+
+
+def loop_switches(db):
+    """The switches that have a link to themselves, ascending."""
+    return sorted(u for u, nb in db.links.items() if u in nb)
+
+
+def step_event_loops(db, rng, dpids, nxt):
+    """step_event with self-loop links mixed in (a cable between two ports of
+    one switch, stored as links[u][u]): with probability 0.3 one existing loop
+    is deleted, re-ported or given a cost, or a loop is added on a random
+    dpid; else step_event.  Returns the kind."""
+    if rng.random() >= 0.3:
+        return step_event(db, rng, dpids, nxt)
+    have = loop_switches(db)
+    k = int(rng.integers(0, 5))
+    if k <= 2 and have:
+        u = have[int(rng.integers(len(have)))]
+        if k == 0:
+            db.delete_link(db.links[u][u])
+            return "loop_delete"
+        if k == 1:
+            db.add_link(Link(Port(u, int(rng.integers(100, 200))), Port(u, 8)))
+            return "loop_report"
+        db.set_link_cost(u, u, int(rng.integers(1, 10)))
+        return "loop_cost"
+    u = int(dpids[int(rng.integers(len(dpids)))])
+    db.add_link(Link(Port(u, 61), Port(u, 62)))
+    return "loop_add"
+
+
 def twin_of(db):
     """A fresh TopologyDB over copies of the live object's dicts and costs,
     with a fresh restatement double: the uncached reference."""
@@ -235,10 +267,13 @@ class Replay(object):
     what was done to it before the run); runs of one tag and seed make the
     same events and draw the same queries, so the twin's answers of a step are
     computed once, checked against the state they were computed from, and
-    left unchanged.  ``costs=False``: topology events only."""
+    left unchanged.  ``costs=False``: topology events only.  ``event``: the
+    step function (step_event, or _events without costs)."""
 
-    def __init__(self, db, seed, fabric, share=None, costs=True):
+    def __init__(self, db, seed, fabric, share=None, costs=True, event=None):
         self.db, self.seed, self.share, self.costs = db, seed, share, costs
+        self.event = event or (step_event if costs else _events)
+        self.with_loop = 0            # compared steps with a self-loop link present
         self.rng = np.random.default_rng(seed)
         self.dpids = [int(d) for d in fabric.csr().dpids]
         self.nxt = [10 ** 6]
@@ -267,7 +302,7 @@ class Replay(object):
         return hit[1]
 
     def step(self):
-        kind = (step_event if self.costs else _events)(self.db, self.rng, self.dpids, self.nxt)
+        kind = self.event(self.db, self.rng, self.dpids, self.nxt)
         self.kinds[kind] += 1
         step = self.steps
         self.steps += 1
@@ -276,6 +311,7 @@ class Replay(object):
         q = draw_queries(self.db, self.rng)
         got = compare(self.db, q, self._reference(q, step), (self.seed, step, kind))
         self.compared += 1
+        self.with_loop += bool(loop_switches(self.db))
         self.no_route += got["no_route"]
         self.all_routed += got["all_routed"]
         self.lost += got["lost"]
@@ -285,13 +321,14 @@ class Replay(object):
     def counters(self):
         return {"kinds": dict(self.kinds), "steps": self.steps, "compared": self.compared,
                 "no_route_steps": self.no_route, "all_routed_steps": self.all_routed,
-                "lost_steps": self.lost, "rows_inherited": self.inherited}
+                "lost_steps": self.lost, "rows_inherited": self.inherited,
+                "loop_steps": self.with_loop}
 
 
-def replay(db, seed, steps, fabric, after_step=None, share=None):
+def replay(db, seed, steps, fabric, after_step=None, share=None, event=None):
     """``steps`` times: one event, then every family against a fresh twin.
     Returns the counters; assertion messages carry (seed, step, kind, family)."""
-    r = Replay(db, seed, fabric, share)
+    r = Replay(db, seed, fabric, share, event=event)
     for _ in range(steps):
         r.step()
         if after_step is not None:
@@ -375,3 +412,40 @@ def test_replay_on_the_restatement_double(name, seed, budget):
     c = replay(db, seed, 40, fabric, after, share=name)
     print("replay %s seed %d budget %s: %r" % (name, seed, budget, c))
     assert_conditions(c)
+
+
+LOOP_STEPS = 60
+LOOP_FABRICS = {"fat_tree:4": (1, 7), TWIN_FREE: (1, 7)}    # seeds that meet the conditions below
+
+
+def assert_loop_conditions(c):
+    """assert_conditions, every kind of self-loop event at least once, and a
+    self-loop link present in at least 40 compared steps."""
+    assert_conditions(c)
+    assert all(c["kinds"].get(k, 0) >= 1 for k in LOOP_KINDS), c
+    assert c["loop_steps"] >= 40, c
+
+
+def loop_ports_are_no_edge_ports(db, r):
+    """Both ports of every self-loop link are link ends: no flood ports."""
+    for u in loop_switches(db):
+        lk = db.links[u][u]
+        assert not db.is_edge_port(lk.src) and not db.is_edge_port(lk.dst), (r.seed, r.steps, u)
+
+
+@pytest.mark.parametrize("budget", ["default", "tiny"])
+@pytest.mark.parametrize("name,seed", [(n, s) for n, seeds in LOOP_FABRICS.items() for s in seeds])
+def test_replay_with_self_loop_events(name, seed, budget):
+    fabric = T.by_name(name)
+    kw = {"table_budget": tiny_budget(fabric)} if budget == "tiny" else {}
+    db = live_db(fabric, FakeFailureEngine(), **kw)
+
+    def after(d, r):
+        loop_ports_are_no_edge_ports(d, r)
+        if kw:
+            within_budget(d, kw["table_budget"])
+
+    c = replay(db, seed, LOOP_STEPS, fabric, after, share=name + "/loops",
+               event=step_event_loops)
+    print("replay %s seed %d budget %s with self-loops: %r" % (name, seed, budget, c))
+    assert_loop_conditions(c)

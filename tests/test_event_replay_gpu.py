@@ -21,8 +21,9 @@ from sdnmpi_amd import topologies as T
 from test_cost_ecmp_loads import random_costs
 from test_ecmp_link_loads import SPLITS, close
 from test_ecmp_link_loads_gpu import dev_dist, zeros_f64
-from test_event_replay import (COST_KINDS, TWIN_FREE, Replay, assert_conditions, live_db,
-                               replay, slot_replay, tiny_budget, within_budget)
+from test_event_replay import (COST_KINDS, LOOP_STEPS, TWIN_FREE, Replay, assert_conditions,
+                               assert_loop_conditions, live_db, loop_ports_are_no_edge_ports,
+                               replay, slot_replay, step_event_loops, tiny_budget, within_budget)
 from test_failure_loads import cable_edges, switch_edges
 from test_failure_loads_gpu import grouped, raw, same
 from test_link_loads_gpu import on
@@ -82,6 +83,28 @@ def test_replay_tiny_budget(eng, name, seed):
     c = replay(db, seed, STEPS, fabric, lambda d, r: within_budget(d, budget), share=name)
     report("%s seed %d tiny budget" % (name, seed), c)
     assert_conditions(c)
+
+
+@pytest.mark.parametrize("budget", ["default", "tiny"])
+@pytest.mark.parametrize("name,seed", [(FAT, 1), (TWIN_FREE, 7)])
+def test_replay_with_self_loop_events(eng, name, seed, budget):
+    """Self-loop links added, deleted, re-ported and costed between the other
+    events (test_event_replay.step_event_loops): the kernels read rows that
+    hold their own vertex, the row test sees (u, u) changes, the cost upload a
+    cost on (u, u), the cable scenarios a one-link cable."""
+    fabric = T.by_name(name)
+    kw = {"table_budget": tiny_budget(fabric)} if budget == "tiny" else {}
+    db = live_db(fabric, eng, **kw)
+
+    def after(d, r):
+        loop_ports_are_no_edge_ports(d, r)
+        if kw:
+            within_budget(d, kw["table_budget"])
+
+    c = replay(db, seed, LOOP_STEPS, fabric, after, share=name + "/loops",
+               event=step_event_loops)
+    report("%s seed %d budget %s with self-loops" % (name, seed, budget), c)
+    assert_loop_conditions(c)
 
 
 def test_replay_one_source_at_a_time(eng):

@@ -105,6 +105,64 @@ def test_batched_events_sound(seed):
         _check(base, _csr(dpids, l2), single=False)
 
 
+# ------------------------------------------------------------ self-loops --
+# A link (u, u) is stored like any other (reference topology_db.py:30-35) and
+# is inert: u is visited when it is popped.  The row test under single
+# self-loop changes is checked against recomputation, not against its twin.
+
+def _loop_cases(seed):
+    """(base CSR with self-loops on a third of the vertices, [(kind, changed
+    CSR)]): one loop removed, one re-ported, one added -- on the root of some
+    row, on an inner vertex, on a leaf or unreached vertex alike, since every
+    vertex is a source."""
+    rng = np.random.default_rng(900 + seed)
+    V = 24
+    dpids = list(range(100, 100 + V))
+    links = _random_directed(V, 60, rng)
+    looped = sorted(int(x) for x in rng.choice(V, V // 3, replace=False))
+    for u in looped:
+        links[(u, u)] = 70
+    base = _csr(dpids, links)
+    out = []
+    for u in (looped[0], looped[len(looped) // 2], looped[-1]):
+        l2 = dict(links)
+        del l2[(u, u)]
+        out.append(("remove", _csr(dpids, l2)))
+        l2 = dict(links)
+        l2[(u, u)] = 170
+        out.append(("report", _csr(dpids, l2)))
+    free = [u for u in range(V) if u not in looped]
+    for u in (free[0], free[len(free) // 2], free[-1]):
+        l2 = dict(links)
+        l2[(u, u)] = 61
+        out.append(("add", _csr(dpids, l2)))
+    return base, out
+
+
+def _dfs_truth(base, new):
+    """bool[V]: the rows of the default-route tables that differ between the
+    two graphs, every vertex a source, by recomputation."""
+    srcs = np.arange(base.V, dtype=np.int32)
+    a = O.dfs_tables(base, srcs, nthreads=4)
+    b = O.dfs_tables(new, srcs, nthreads=4)
+    return a, ((a[0] != b[0]) | (a[1] != b[1]) | (a[2] != b[2])).any(1)
+
+
+@pytest.mark.parametrize("seed", range(3))
+def test_self_loop_events_host_exact(seed):
+    base, cases = _loop_cases(seed)
+    srcs = np.arange(base.V)
+    for kind, new in cases:
+        (p, t, h), truth = _dfs_truth(base, new)
+        assert (p[srcs, srcs] == srcs).all()          # the root's parent is itself
+        diff = edge_diff(base, new)
+        assert sum(x[0].size for x in (diff.removed, diff.ported, diff.added)) == 1
+        got = np.asarray(dfs_rows_affected(p, h, srcs, diff), bool)
+        np.testing.assert_array_equal(got, truth, err_msg=kind)
+        assert not truth.any(), kind                  # a self-loop is inert
+        _check(base, new, single=True)
+
+
 def test_fat_tree_link_failure_touches_few_rows():
     """A failed agg-core link (both directions, as Ryu reports it) on the
     k=8 fat-tree: only the sources whose tree uses it are recomputed."""
@@ -257,3 +315,18 @@ def test_device_row_test_fabrics(gctx, fab):
         for layout in ("port16", "slot"):
             got = _device_verdict(gctx, csr, new, p, t, h, srcs, diff, layout)
             np.testing.assert_array_equal(got, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["port16", "slot", "int32"])
+@pytest.mark.parametrize("seed", range(3))
+def test_device_row_test_exact_under_self_loops(gctx, seed, layout):
+    """One self-loop removed, re-ported or added on a graph that holds
+    self-loops: the kernel's verdict equals recomputation (no row changes)."""
+    base, cases = _loop_cases(seed)
+    srcs = np.arange(base.V, dtype=np.int32)
+    for kind, new in cases:
+        (p, t, h), truth = _dfs_truth(base, new)
+        diff = edge_diff(base, new)
+        got = _device_verdict(gctx, base, new, p, t, h, srcs, diff, layout)
+        np.testing.assert_array_equal(got, truth, err_msg=kind)
