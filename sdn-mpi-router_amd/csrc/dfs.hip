@@ -2470,7 +2470,9 @@ static int dfs_async_waves(const sdnr_ctx *ctx, int nsrc)
     // slower once every CU holds several sources (k=48 1,152: 91.6 -> 137 us
     // with 4 workers), where the workers compete with the search waves.
     // Round 4: with the dword-paired rows (in-degree > 32) 7 workers -- k=48
-    // 144 / 1 sources 48.8 / 47.1 -> 46.9 / 45.1 us
+    // 144 / 1 sources 48.8 / 47.1 -> 46.9 / 45.1 us.  nsrc: the searches
+    // that run -- a folded search's published live count where dfs_dispatch
+    // has one (k=48 1,152 sources, 48 live: 63.4 -> 56.4 us at 8, 58.1 at 6)
     if (nsrc <= 2 * ctx->num_cus) return ctx->radj_pair ? 6 : 8;
     return ctx->max_deg <= 32 ? 3 : 4;
 }
@@ -2786,11 +2788,14 @@ static bool dfs_async(const sdnr_ctx *ctx, int nsrc, bool hops)
 // the strategy dispatch: one search per entry of d_src.  d_live (device, may
 // be null): only the first min(nsrc, *d_live) entries are searched and only
 // their rows written -- honoured where dfs_takes_live() says so, else every
-// entry is searched, so the caller pads the list with -1 (empty rows)
+// entry is searched, so the caller pads the list with -1 (empty rows).
+// live_n (with low; 0: none): the published live count the caller took the
+// low-load form from -- dfs_async_kernel is then dispatched as live_n
+// searches select it, not as nsrc does
 static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
                         int32_t *d_parent, int32_t *d_port, int32_t *d_hops, uint32_t *d_tree,
                         bool slots = false, bool hops16 = false,
-                        const int32_t *d_live = nullptr, bool low = false)
+                        const int32_t *d_live = nullptr, bool low = false, int32_t live_n = 0)
 {
     const int V = ctx->V;
     if (nsrc == 0 || V == 0) return SDNR_OK;
@@ -2888,25 +2893,42 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
     const bool coop = !count && coop_ok && (force ? !strcmp(force, "coop") : small);
     if (async) {
         int *err = ctx->d_err;
-        const int nw = dfs_async_waves(ctx, nsrc);
-        // workgroups per CU: LDS, and the 32 wave slots; the compact layout
-        // (u16 counts, u16 parents + u8 slots) where it holds more sources
-        // at once and the full layout cannot hold them all (dragonfly 2,064
-        // sources: 9 x 3 waves per CU vs 6); SDNROUTE_DFS_C16=0|1 forces it
-        auto per_cu = [&](bool c) {
+        // workgroups per CU at w waves: LDS, and the 32 wave slots; the
+        // compact layout (u16 counts, u16 parents + u8 slots) where it holds
+        // more sources at once and the full layout cannot hold them all
+        // (dragonfly 2,064 sources: 9 x 3 waves per CU vs 6);
+        // SDNROUTE_DFS_C16=0|1 forces it
+        auto per_cu = [&](int w, bool c) {
             size_t b = SDNR_LDS_PER_CU / dfs_lds_bytes_async(V, hops, c);
-            if (b > (size_t)(32 / nw)) b = 32 / nw;
+            if (b > (size_t)(32 / w)) b = 32 / w;
             return b < 1 ? (size_t)1 : b;
         };
-        bool c16 = per_cu(true) > per_cu(false) &&
-                   (size_t)ctx->num_cus * per_cu(false) < (size_t)nsrc;
-        if (const char *f = getenv("SDNROUTE_DFS_C16")) c16 = !strcmp(f, "1");
-        const size_t cl = dfs_lds_bytes_async(V, hops, c16);
-        const size_t cpc = per_cu(c16);
+        auto compact = [&](int w) {
+            bool c = per_cu(w, true) > per_cu(w, false) &&
+                     (size_t)ctx->num_cus * per_cu(w, false) < (size_t)nsrc;
+            if (const char *f = getenv("SDNROUTE_DFS_C16")) c = !strcmp(f, "1");
+            return c;
+        };
         // pre-swizzled worker rows (SDNROUTE_DFS_PRESWZ=0 keeps the plain ones)
         const char *pz = getenv("SDNROUTE_DFS_PRESWZ");
-        const uint16_t *rw = c16 ? ctx->radjc : ctx->radjw;
-        const bool preswz = rw && !(pz && !strcmp(pz, "0"));
+        auto rows_of = [&](bool c) { return c ? ctx->radjc : ctx->radjw; };
+        auto preswz_of = [&](bool c) { return rows_of(c) && !(pz && !strcmp(pz, "0")); };
+        // the wave count: the caller's nsrc selects it, or -- the folded
+        // search in its low-load form, taken from a published live count --
+        // that count (48 live searches of 1,152 sources: 7 workers each, not
+        // 3), where the rows are then neither compact nor paired; all that
+        // follows from nw follows it
+        int nw = dfs_async_waves(ctx, nsrc);
+        if (low && d_live && live_n > 0) {
+            const int cw = dfs_async_waves(ctx, live_n);
+            const bool cc = compact(cw);
+            if (!cc && !(preswz_of(cc) && ctx->radj_pair)) nw = cw;
+        }
+        const bool c16 = compact(nw);
+        const size_t cl = dfs_lds_bytes_async(V, hops, c16);
+        const size_t cpc = per_cu(nw, c16);
+        const uint16_t *rw = rows_of(c16);
+        const bool preswz = preswz_of(c16);
         // speculative stack pops (SDNROUTE_DFS_SPECPOP=0|1).
         // Compiled into the 4-wave plain-row kernel only (the k=48
         // headline's regime: 1,152 sources 83.0 -> 82.3 us, same ISA with
@@ -2928,14 +2950,17 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
         bool dw = preswz && !pair && !c16 && nw >= 6;
         if (dq) dw = preswz && !pair && !c16 && !strcmp(dq, "1");
         // the folded search's low-load form (sdnr_launch_dfs asks for it when
-        // few searches are live): nw, the grid and the name stay the caller's
-        // nsrc's, only the instantiation differs, and both are bit-exact
+        // few searches are live): another instantiation, bit-exact with the
+        // full-load one.  A forced form has no count: nw, the grid and the
+        // name stay the caller's nsrc's
         if (low && d_live && !c16 && !pair) {
             if (SDNR_FOLD_LOW_FORM & 1) spec = false;
             if (SDNR_FOLD_LOW_FORM & 2) dw = preswz;
             ctx->dfs_form = kDfsFormLow;
         }
         int cgrid = (int)((size_t)ctx->num_cus * cpc);
+        // (a count-selected grid capped at kFoldLowPerCu per CU, 512 for 1,024
+        // workgroups of which 48 search: 57.7 against 57.5 us, not kept)
         if (cgrid > nsrc) cgrid = nsrc;
         // the search wave issues at raised priority over the decrement
         // workers (dragonfly 0.316 -> 0.300 ms, k=48 unchanged)
@@ -3389,12 +3414,15 @@ static bool dfs_takes_live(const sdnr_ctx *ctx, int nsrc, bool hops, bool packed
     return dfs_async(ctx, nsrc, hops) && !(packed && slots);
 }
 
-// fold this batch?  Only a graph with twins, and by default only above 2.5
-// sources per CU, the measured crossover at k=48 (forced on,
-// 144 / 288 / 516 / 576 sources lose 6.6 / 0.8 / 0.6 us or tie, 720 / 864 /
-// 1,152 gain): below it one launch runs near the single-source chain time
-// and the fold only adds its two launches.  SDNROUTE_DFS_FOLD=0|1 forces it
-// off / on (A/B, tests on tiny batches)
+// fold this batch?  Only a graph with twins, and by default only above 2
+// sources per CU, the boundary dfs_async_waves uses.  Up to
+// it the batch size itself selects the 8-wave kernel and the fold only adds
+// its two launches (forced on, k=48 144 / 288 sources lose 6.6 / 0.8 us);
+// above it the folded search runs 8 waves from its second call on, the
+// unfolded one 4: 516 / 576 / 640 sources 52.9 / 53.4 / 53.6 us folded, 63.6 /
+// 65.0 / 65.1 not (profiles/fold_waves_ab.txt; with the folded search at 4
+// waves 516 and 576 tied, and the constant was 2.5).  SDNROUTE_DFS_FOLD=0|1
+// forces it off / on (A/B, tests on tiny batches)
 static bool dfs_fold(const sdnr_ctx *ctx, int nsrc)
 {
     if (!ctx->has_twins) return false;
@@ -3402,7 +3430,7 @@ static bool dfs_fold(const sdnr_ctx *ctx, int nsrc)
         if (!strcmp(f, "0")) return false;
         if (!strcmp(f, "1")) return true;
     }
-    return 2 * (int64_t)nsrc > 5 * (int64_t)ctx->num_cus;
+    return (int64_t)nsrc > 2 * (int64_t)ctx->num_cus;
 }
 
 // live searches per CU up to which the folded search takes its low-load form:
@@ -3415,9 +3443,11 @@ static bool dfs_fold(const sdnr_ctx *ctx, int nsrc)
 constexpr int kFoldLowPerCu = 2;
 
 // the folded search in its low-load form?  SDNROUTE_DFS_FOLD_FORM=full|low
-// forces either (A/B, tests)
-static bool dfs_fold_low(sdnr_ctx *ctx, int nsrc)
+// forces either (A/B, tests).  *count: the published count the answer was
+// taken from, 0 where it was forced
+static bool dfs_fold_low(sdnr_ctx *ctx, int nsrc, int32_t *count)
 {
+    *count = 0;
     if (const char *f = getenv("SDNROUTE_DFS_FOLD_FORM")) {
         if (!strcmp(f, "full")) return false;
         if (!strcmp(f, "low")) return true;
@@ -3425,15 +3455,19 @@ static bool dfs_fold_low(sdnr_ctx *ctx, int nsrc)
     // the count the derive kernel of an earlier folded call published: read
     // once, never waited for.  It counts only when its sequence number is a
     // launch of this graph upload with this nsrc (live_ring); a stale or
-    // missing one only picks the slower of two bit-exact instantiations --
+    // missing one only picks a slower one of several bit-exact kernels --
     // the search itself reads the count from the device
     const unsigned long long w = __atomic_load_n(ctx->h_live, __ATOMIC_RELAXED);
     const uint32_t seq = (uint32_t)(w >> 32);
     if (seq == 0) return false;
     for (const auto &r : ctx->live_ring)
-        if (r.seq0 && seq - r.seq0 <= r.seq1 - r.seq0)       // the run that launch was in
-            return r.gen == ctx->upload_gen && r.nsrc == nsrc &&
-                   (int64_t)(uint32_t)w <= (int64_t)kFoldLowPerCu * ctx->num_cus;
+        if (r.seq0 && seq - r.seq0 <= r.seq1 - r.seq0) {     // the run that launch was in
+            if (r.gen != ctx->upload_gen || r.nsrc != nsrc ||
+                (int64_t)(uint32_t)w > (int64_t)kFoldLowPerCu * ctx->num_cus)
+                return false;
+            *count = (int32_t)(uint32_t)w;
+            return true;
+        }
     return false;
 }
 
@@ -3480,7 +3514,8 @@ int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
     // a strategy that honours the live count searches the leaders only; any
     // other gets the list padded with -1, so that its rows stay defined
     const bool live = (SDNR_FOLD_PARTS & 1) && dfs_takes_live(ctx, nsrc, hbytes != 0, packed, slots);
-    const bool low = live && dfs_fold_low(ctx, nsrc);
+    int32_t live_n = 0;                          // the published count, where the form is its choice
+    const bool low = live && dfs_fold_low(ctx, nsrc, &live_n);
     uint32_t seq = 0;                            // this launch in the ring of published counts
     if (live) {
         if (!(seq = ++ctx->live_seq)) seq = ++ctx->live_seq;
@@ -3505,7 +3540,7 @@ int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
     ctx->timed = false;                          // the span is timed around the three launches
     rc = dfs_dispatch(ctx, csrc, nsrc, packed ? nullptr : t0, t1, th,
                       packed ? reinterpret_cast<uint32_t *>(t0) : nullptr, slots, hops16,
-                      live ? count : nullptr, low);
+                      live ? count : nullptr, low, live_n);
     ctx->timed = timed;
     if (rc) return rc;
     uint32_t *o0 = packed ? d_tree : reinterpret_cast<uint32_t *>(d_parent);

@@ -74,7 +74,7 @@ def main():
         print("opened %s" % p, file=sys.stderr, flush=True)
     res = {p: {} for p in libs}
     only = os.environ.get("AB_NS")            # e.g. "144,1152": these counts only
-    ns = [n for n in (1, 8, 32, 144, 258, 288, 516, 576, 720, 864, 1008, 1152, len(srcs))
+    ns = [n for n in (1, 8, 32, 144, 258, 288, 516, 576, 640, 720, 864, 1008, 1152, len(srcs))
           if n <= len(srcs)]
     if only:
         ns = [n for n in ns if str(n) in only.split(",") or (n == len(srcs) and "all" in only)]
