@@ -227,7 +227,10 @@ int sdnr_dfs_rows_affected(sdnr_ctx *ctx, const uint32_t *tree, const void *dept
  *   nh_port[i*V+x]  links[x][nh].src.port_no.
  * Following nh from x gives routes[0] (the lexicographically smallest
  * shortest path); the shortest-path DAG in dist gives the whole ECMP set in
- * the reference's order.  nh / nh_port may be NULL (distances only). */
+ * the reference's order.  nh / nh_port may be NULL (distances only).
+ * A u16 distance holds at most 65,534 hops: the level loops stop there, and a
+ * vertex farther from dst[i] reads SDNR_DIST_INF and nh -1, as an unreachable
+ * one does (only a graph of more than 65,535 vertices can hold one). */
 int sdnr_shortest_tables(sdnr_ctx *ctx, const int32_t *dst, int32_t ndst,
                          uint16_t *dist, int32_t *nh, int32_t *nh_port,
                          uint32_t flags);
@@ -325,8 +328,9 @@ int sdnr_route_expand(sdnr_ctx *ctx, const int32_t *parent, const int32_t *port,
  * packed tree word's layout: a dense switch id and a 16-bit OpenFlow 1.0
  * port, OFPP_LOCAL = 0xfffe included) -- half the bytes of the two int32
  * arrays.  Needs V <= 65535 and 16-bit link ports (else SDNR_ERR_INVAL);
- * a last (host) port above 0xffff keeps only its low 16 bits, so callers
- * with such ports use sdnr_route_expand (the drop-in does).  Device
+ * a last (host) port outside [0, 0xfffe] fails the call (sdnr_synchronize
+ * reports SDNR_ERR_INVAL; 0xffff is the word's "no port", as in the packed
+ * tree), so callers with such ports use sdnr_route_expand (the drop-in does).  Device
  * pointers only (flags must hold SDNR_DEVICE_PTRS). */
 int sdnr_route_expand_packed(sdnr_ctx *ctx, const int32_t *parent, const int32_t *port,
                              int32_t nrows, const int32_t *rows, const int32_t *dsts,

@@ -96,7 +96,7 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "tables invalid");
         if (h & kErrLastPort)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_route_expand_packed: a last port outside "
-                             "[0, 0xFFFF] (u32 entries hold 16-bit ports): entries invalid");
+                             "[0, 0xFFFE] (u32 entries hold 16-bit ports, 0xFFFF is no port): entries invalid");
         return sdnr_fail(SDNR_ERR_HIP, "kernel watchdog tripped (code %d): results invalid", h);
     }
     return SDNR_OK;
@@ -653,7 +653,8 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
         }
         // narrow ELL ids for the large-graph DFS: u16 (V <= 65535: id 0xFFFF is
         // free for padding), or 16 low bits + a per-row mask of bit 16
-        // (V <= 131071, rows <= 32 slots); padding decodes to an id >= V
+        // (65535 < V <= 131071, rows <= 32 slots); padding decodes to 0x1FFFF,
+        // an id >= V
         if (V <= 131071 && W <= 32) {
             std::vector<uint16_t> e16(ec.size() + kPad, (uint16_t)0xFFFF);
             std::vector<uint32_t> hi(V > 65535 ? (size_t)V + kPad : 0, 0u);

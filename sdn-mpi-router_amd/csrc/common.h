@@ -60,7 +60,7 @@ struct sdnr_ctx {
     bool has_cost = false;              // costs uploaded for this graph (E may be 0)
     int32_t *ell_col = nullptr, *ell_port = nullptr;
     uint16_t *ell16 = nullptr;          // ELL ids as u16 (low 16 bits when V > 65535), 0xFFFF pad
-    uint32_t *ell_hi = nullptr;         // per row: the 17th id bit of each slot (65535 <= V < 131071)
+    uint32_t *ell_hi = nullptr;         // per row: the 17th id bit of each slot (65535 < V <= 131071)
     // dictionary rows for the split DFS (V <= 65535, rows of <= 8 slots):
     // row u = u + dict_off[p(u) * 8 + slot], p(u) = byte (u & 31) of block
     // tuple dict_bt[b(u)] (32 pattern bytes = 8 u32 words), b(u) = byte
@@ -194,7 +194,7 @@ inline const char *sdnr_tune_env(const char *name)
 constexpr int kDfsFormFull = 0, kDfsFormLow = 1;   // sdnr_ctx::dfs_form (sdnr_last_dfs_form)
 constexpr int kDictPad = 0x40000000;   // dictionary-row padding offset (u + pad >= V)
 constexpr int kDictMaxP = 255;         // pattern ids are bytes
-constexpr int kErrLastPort = 256;   // sdnr_route_expand_packed: a last port outside [0, 0xFFFF]
+constexpr int kErrLastPort = 256;   // sdnr_route_expand_packed: a last port outside [0, 0xFFFE]
 constexpr int kErrTreeClimb = 512;  // sdnr_dfs_rows_affected: a tree climb outran V steps
 constexpr int kErrScan = 1024;      // sdnr_route_offsets: a look-back wait ran out
 constexpr int kErrSeg = 2048;       // route expansion: a walker / storer hand-off wait ran out

@@ -2589,7 +2589,7 @@ static int launch_split_ns(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc, in
     if (tree == kTreePort16 && fmt != kRow16)
         return sdnr_fail(SDNR_ERR_INVAL, "dfs split: packed tables need V <= 65535");
     if (tree == kTreeSlot && hops && fmt == kRow32)
-        return sdnr_fail(SDNR_ERR_INVAL, "dfs split: slot trees with hop counts need V < 131071");
+        return sdnr_fail(SDNR_ERR_INVAL, "dfs split: slot trees with hop counts need V <= 131071");
     // dictionary rows where the upload built them (rows of <= 8 slots)
     const bool dict = ctx->dict_bp && lpr == 8 && !kWide;
     const size_t dict_words =

@@ -461,11 +461,11 @@ __global__ __launch_bounds__(256) void route_seg_packed_kernel(
                 lo = off[i];
                 L = (int)(off[i + 1] - lo);
             }
-            // u32 entries hold a 16-bit port: a last (host) port outside
-            // [0, 0xFFFF] cannot be written -- fail the call (watchdog code
-            // kErrLastPort, reported by sdnr_synchronize) instead of keeping
-            // its low bits
-            if (OUTP && __ballot(L > 0 && (uint32_t)lp > 0xFFFFu) && lane == 0)
+            // u32 entries hold a 16-bit port, 0xFFFF the word's "no port" as in
+            // the packed tree: a last (host) port outside [0, 0xFFFE] cannot be
+            // written -- fail the call (watchdog code kErrLastPort, reported
+            // by sdnr_synchronize) instead of keeping its low bits
+            if (OUTP && __ballot(L > 0 && (uint32_t)lp >= 0xFFFFu) && lane == 0)
                 atomicOr(err, kErrLastPort);
             const int pl = L > 0 ? L - 1 : 0;       // path entries before the last
             const int pr = __shfl_up(r, 1, 64), pd = __shfl_up(d, 1, 64);
@@ -734,7 +734,7 @@ __global__ __launch_bounds__((NWK + NST) * 64) void route_seg_pipe_kernel(
                     lo = off[i];
                     L = (int)(off[i + 1] - lo);
                 }
-                if (OUTP && __ballot(L > 0 && (uint32_t)lp > 0xFFFFu) && lane == 0)
+                if (OUTP && __ballot(L > 0 && (uint32_t)lp >= 0xFFFFu) && lane == 0)
                     atomicOr(err, kErrLastPort);
                 const int pl = L > 0 ? L - 1 : 0;
                 const int pr = __shfl_up(r, 1, 64), pd = __shfl_up(d, 1, 64);

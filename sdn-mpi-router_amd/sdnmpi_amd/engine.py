@@ -1149,7 +1149,7 @@ class RouteEngine(object):
         lp = np.asarray(last_port)
         env = os.environ.get
         if tree_layout(export.csr) == PORT16 and (lp.size == 0 or
-                                                  (lp.min() >= 0 and lp.max() <= 0xFFFF)) \
+                                                  (lp.min() >= 0 and lp.max() < 0xFFFF)) \
                 and env("SDNROUTE_ROUTE_OUT", "") != "int32" \
                 and env("SDNROUTE_ROUTE_WALK", "") != "serial" and env("SDNROUTE_ROUTE_SEG", "") != "0" \
                 and env("SDNROUTE_ROUTE_PACKED", "") != "0":
@@ -2087,22 +2087,30 @@ def shortest_paths_lex(row_ptr, col, dist_row, s, d):
         return []
     if count_shortest_paths(row_ptr, col, dist_row, s, d, ECMP_LIMIT) > ECMP_LIMIT:
         raise MemoryError("ECMP set too large to enumerate")
-    out = []
-    acc = [int(s)]
+    s, d = int(s), int(d)
+    if s == d:
+        return [[s]]
 
-    def walk(x):
-        if x == d:
-            out.append(list(acc))
-            return
+    def hops(x):
         want = int(dist_row[x]) - 1
-        for e in range(int(row_ptr[x]), int(row_ptr[x + 1])):
-            n = int(col[e])
-            if int(dist_row[n]) == want:
-                acc.append(n)
-                walk(n)
-                acc.pop()
+        return (int(col[e]) for e in range(int(row_ptr[x]), int(row_ptr[x + 1]))
+                if int(dist_row[int(col[e])]) == want)
 
-    walk(int(s))
+    out = []
+    # (iterative: a shortest route may be tens of thousands of links long)
+    acc, stack = [s], [hops(s)]
+    while stack:
+        n = next(stack[-1], None)
+        if n is None:
+            stack.pop()
+            acc.pop()
+            continue
+        acc.append(n)
+        if n == d:
+            out.append(list(acc))
+            acc.pop()
+            continue
+        stack.append(hops(n))
     return out
 
 
