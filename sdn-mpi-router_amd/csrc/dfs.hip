@@ -3265,63 +3265,128 @@ __global__ __launch_bounds__(kFoldPrepThreads) void dfs_fold_prep_kernel(
     if (tid == 0) count[0] = base;
 }
 
+constexpr int kFoldPatchCap = kFoldDeriveThreads + 4;    // a chunk of a row's patch list, + ls
+static_assert(kFoldDeriveThreads % SDNR_WAVE == 0 &&
+              (kFoldDeriveThreads & (kFoldDeriveThreads - 1)) == 0, "owner rule: x >> shift & (threads - 1)");
+
+// patch stores overlap the 16-byte copy stores of the same wave
+typedef uint32_t __attribute__((may_alias)) fold_u32;
+typedef uint16_t __attribute__((may_alias)) fold_u16;
+
+// a barrier on LDS alone: no wait for the global stores in flight
+__device__ __forceinline__ void fold_lds_barrier()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// the value is in its registers here: the compiler moves its load no further
+__device__ __forceinline__ void fold_pin(uint4 &v)
+{
+    asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
+}
+__device__ __forceinline__ void fold_pin(uint32_t &v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void fold_pin(uint16_t &v)
+{
+    uint32_t x = v;
+    asm volatile("" : "+v"(x));
+    v = (uint16_t)x;
+}
+
+// a row of n elements at out, a copy of the row at in (nullptr: every element
+// `ones`, an empty row in every layout): element k by thread k % threads
+template <typename T>
+__device__ __forceinline__ void fold_copy_elems(const T *__restrict__ in, T *__restrict__ out,
+                                                size_t n, T ones)
+{
+    constexpr size_t nt = kFoldDeriveThreads;
+    if (!in) {
+        for (size_t k = threadIdx.x; k < n; k += nt) out[k] = ones;
+        return;
+    }
+    for (size_t k0 = threadIdx.x; k0 < n; k0 += 4 * nt) {    // four loads in flight
+        const size_t k1 = k0 + nt, k2 = k1 + nt, k3 = k2 + nt;
+        T v0 = in[k0], v1 = in[k1 < n ? k1 : k0], v2 = in[k2 < n ? k2 : k0],
+          v3 = in[k3 < n ? k3 : k0];
+        // every load is issued, and has landed, before the first store: a
+        // load left behind a store (sunk into its branch), or pending behind
+        // a skipped one, is waited for with a count that the stores in flight
+        // have to reach too
+        fold_pin(v0);
+        fold_pin(v1);
+        fold_pin(v2);
+        fold_pin(v3);
+        out[k0] = v0;
+        if (k1 < n) out[k1] = v1;
+        if (k2 < n) out[k2] = v2;
+        if (k3 < n) out[k3] = v3;
+    }
+}
+
 // a row of `bytes` bytes: 16 bytes per thread and step when vec (row size and
-// both tables 16-byte aligned), else in elements of es (2 or 4) bytes; in ==
-// nullptr fills the row with 0xFF bytes (an empty row in every layout)
+// both tables 16-byte aligned), else in elements of es (2 or 4) bytes
 __device__ __forceinline__ void fold_copy_row(const char *__restrict__ in, char *__restrict__ out,
                                               size_t bytes, int es, bool vec)
 {
-    const int tid = (int)threadIdx.x;
-    constexpr int nt = kFoldDeriveThreads;
-    if (vec) {
-        const uint4 ones = make_uint4(~0u, ~0u, ~0u, ~0u);
-        const uint4 *i4 = reinterpret_cast<const uint4 *>(in);
-        uint4 *o4 = reinterpret_cast<uint4 *>(out);
-        for (size_t k = tid; k < bytes / 16; k += nt) o4[k] = in ? i4[k] : ones;
-    } else if (es == 4) {
-        const uint32_t *i1 = reinterpret_cast<const uint32_t *>(in);
-        uint32_t *o1 = reinterpret_cast<uint32_t *>(out);
-        for (size_t k = tid; k < bytes / 4; k += nt) o1[k] = in ? i1[k] : ~0u;
-    } else {
-        const uint16_t *i1 = reinterpret_cast<const uint16_t *>(in);
-        uint16_t *o1 = reinterpret_cast<uint16_t *>(out);
-        for (size_t k = tid; k < bytes / 2; k += nt) o1[k] = in ? i1[k] : (uint16_t)0xFFFF;
-    }
+    if (vec)
+        fold_copy_elems(reinterpret_cast<const uint4 *>(in), reinterpret_cast<uint4 *>(out),
+                        bytes / 16, make_uint4(~0u, ~0u, ~0u, ~0u));
+    else if (es == 4)
+        fold_copy_elems(reinterpret_cast<const uint32_t *>(in), reinterpret_cast<uint32_t *>(out),
+                        bytes / 4, ~0u);
+    else
+        fold_copy_elems(reinterpret_cast<const uint16_t *>(in), reinterpret_cast<uint16_t *>(out),
+                        bytes / 2, (uint16_t)0xFFFF);
 }
 
-// one patched entry in the layout's encoding (par < 0: unreached)
-__device__ __forceinline__ void fold_put(int fmt, int hbytes, uint32_t *__restrict__ out0,
-                                         uint32_t *__restrict__ out1, char *__restrict__ outh,
-                                         size_t e, int par, int prt, int slot, int hop)
+// one patched entry in the layout's encoding (par < 0: unreached): the words
+// of table 0, table 1 (int32 layout) and the depth plane
+__device__ __forceinline__ void fold_encode(int fmt, int hbytes, int par, int prt, int slot,
+                                            int hop, uint32_t *w0, uint32_t *w1, uint32_t *wh)
 {
-    if (fmt == kTreeInt32) {
-        out0[e] = (uint32_t)par;
-        out1[e] = (uint32_t)(par < 0 ? -1 : prt);
-    } else if (par < 0) {
-        out0[e] = 0xFFFFFFFFu;
-    } else if (fmt == kTreePort16) {
-        out0[e] = ((uint32_t)par & 0xFFFFu) | ((uint32_t)prt << 16);
-    } else {
-        out0[e] = (uint32_t)par | ((uint32_t)slot << 26);
-    }
-    if (hbytes == 2) reinterpret_cast<uint16_t *>(outh)[e] = (uint16_t)(par < 0 ? -1 : hop);
-    else if (hbytes == 4) reinterpret_cast<int32_t *>(outh)[e] = par < 0 ? -1 : hop;
+    if (fmt == kTreeInt32) *w1 = (uint32_t)(par < 0 ? -1 : prt);
+    if (fmt == kTreeInt32) *w0 = (uint32_t)par;
+    else if (par < 0) *w0 = 0xFFFFFFFFu;
+    else if (fmt == kTreePort16) *w0 = ((uint32_t)par & 0xFFFFu) | ((uint32_t)prt << 16);
+    else *w0 = (uint32_t)par | ((uint32_t)slot << 26);
+    if (hbytes) *wh = (uint32_t)(par < 0 ? -1 : hop);
+}
+
+// the lanes of a wave hold one patch each (column x, -1: none; word wv): the
+// patches whose words this wave copied -- thread x >> shift & (threads - 1)
+// is one of its -- go out in one store, after the wave's copy stores.  Two
+// entries with one column in a store (parallel links in row(s)) leave it to
+// the hardware which lane's word stays, as one store per thread always did
+template <typename T>
+__device__ __forceinline__ void fold_apply(int x, uint32_t wv, int shift, T *row)
+{
+    const int w = (int)threadIdx.x / SDNR_WAVE;
+    if (x >= 0 && ((x >> shift) & (kFoldDeriveThreads - 1)) / SDNR_WAVE == w) row[x] = (T)wv;
 }
 
 // one workgroup per caller row i: the leader's row, then -- for a row that is
-// not its leader's own -- the patched entries, each stored by one thread
-// after the copy (workgroup barrier: the later store to the same word wins).
-// With ls the leader's source and s this row's:
+// not its leader's own -- the patched entries.  With ls the leader's source
+// and s this row's:
 //   v in row(s)  parent s, the port / slot of s's link to v, hops 1
 //   v == s       the root
 //   v == ls      what the leader's row holds for s, the port / slot that of
 //                the same parent's link to ls (it exists: equal in-rows)
-// The patches are worked out before the copy, so their loads (the last wave
-// looks ls up in the parent's row, a lane per entry) do not queue behind it.
+// kFoldDeriveThreads threads copy and load nothing but lead / src / lsrc and
+// the leader's row; one wave more, the patch wave, works the patches out
+// meanwhile (a lane per entry of row(s), and per entry of the parent's row in
+// the search for ls) and hands them over in LDS, a list of (column, encoded
+// words) and its length.  After a barrier on LDS alone every patch is stored
+// by the copy wave one of whose threads' stores covered its word, after that
+// store: a wave's stores to one address take effect in issue order, so
+// nothing waits for the copy stores' acknowledgement (by the owning thread
+// alone, one store instruction a patch, the partial writes of one cache line
+// queue behind each other: DESIGN.md 4.1e).  A row with more than
+// kFoldDeriveThreads patches takes its list in chunks.
 // fmt: table 0 is int32 parents (table 1 the ports), parent | port << 16, or
 // parent | slot << 26; hbytes: 0 (no hop table), 2 or 4; vec: bit k set when
 // table k (2: hops) takes the 16-byte copy
-__global__ __launch_bounds__(kFoldDeriveThreads) void dfs_fold_derive_kernel(
+__global__ __launch_bounds__(kFoldDeriveThreads + SDNR_WAVE) void dfs_fold_derive_kernel(
     int V, int fmt, int hbytes, int vec, const int32_t *__restrict__ src,
     const int32_t *__restrict__ lsrc, const int32_t *__restrict__ lead,
     const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
@@ -3330,9 +3395,15 @@ __global__ __launch_bounds__(kFoldDeriveThreads) void dfs_fold_derive_kernel(
     const char *__restrict__ inh, char *__restrict__ outh, const int32_t *__restrict__ count,
     unsigned long long *pub, uint32_t seq)
 {
-    constexpr int kLast = kFoldDeriveThreads - SDNR_WAVE;    // first thread of the last wave
+    constexpr int nt = kFoldDeriveThreads;
+    __shared__ int32_t p_col[kFoldPatchCap];     // the patch list: column (-1: none),
+    __shared__ uint32_t p_w0[kFoldPatchCap];     // the word of every table,
+    __shared__ uint32_t p_w1[kFoldPatchCap];
+    __shared__ uint32_t p_wh[kFoldPatchCap];
+    __shared__ int32_t p_d;                      // and |row(s)|
     const size_t i = blockIdx.x;
-    const int tid = (int)threadIdx.x;
+    const int tid = (int)threadIdx.x, lane = lane_id();
+    const bool patcher = uniform(tid / SDNR_WAVE) == nt / SDNR_WAVE;
     // pub (a coherent host word, may be null): the live count of this call
     // for the host's choice of the next call's search form, one 8-byte store
     // by one thread; its acknowledgement is waited for under the copy
@@ -3344,43 +3415,89 @@ __global__ __launch_bounds__(kFoldDeriveThreads) void dfs_fold_derive_kernel(
                            __HIP_MEMORY_SCOPE_SYSTEM);
     const bool patch = L >= 0 && s != ls;        // else an empty row, or the leader's as it is
     const size_t ob = i * (size_t)V, lb = (size_t)(L < 0 ? 0 : L) * (size_t)V;
-    int a = 0, d = 0;
-    int av = -1, apar = s, aprt = -1, aslot = 63, ahop = 0;      // row(s) / the root
-    int bv = -1, bpar = -1, bprt = -1, bslot = 63, bhop = -1;    // ls
-    if (patch) {
-        a = row_ptr[s];
-        d = row_ptr[s + 1] - a;
-        if (tid < d) {
-            av = col[a + tid];
-            aprt = port[a + tid];
-            aslot = tid;
-            ahop = 1;
-        } else if (tid == d) {
-            av = s;
-        }
-        if (tid >= kLast) {
-            const int lane = tid - kLast;
-            const uint32_t e = in0[lb + s];
-            const int par = fmt == kTreeInt32 ? (int)e
-                            : e == 0xFFFFFFFFu ? -1
-                            : (int)(e & (fmt == kTreePort16 ? 0xFFFFu : 0x3FFFFFFu));
-            int hop = -1;
-            if (hbytes == 2) hop = reinterpret_cast<const uint16_t *>(inh)[lb + s];
-            else if (hbytes == 4) hop = reinterpret_cast<const int32_t *>(inh)[lb + s];
-            if (par < 0) {
-                if (lane == 0) bv = ls;
-            } else {
-                const int lo = row_ptr[par], n = row_ptr[par + 1] - lo;
-                for (int k = lane; k < n; k += SDNR_WAVE)
-                    if (col[lo + k] == ls) {
-                        bv = ls;
-                        bpar = par;
-                        bprt = port[lo + k];
-                        bslot = k;
-                        bhop = hop;
-                    }
+    // the patch wave and the copy waves meet at barriers of their own, so
+    // that neither's waits are merged into the other's path (patcher is
+    // wave-uniform, and a scalar branch)
+    if (patcher) {
+        if (!patch) return;
+        // first trip: what the leader's row holds for s, and row(s)'s bounds
+        const uint32_t e = in0[lb + s];
+        int hop = -1;
+        if (hbytes == 2) hop = reinterpret_cast<const uint16_t *>(inh)[lb + s];
+        else if (hbytes == 4) hop = reinterpret_cast<const int32_t *>(inh)[lb + s];
+        const int a = uniform(row_ptr[s]), d = uniform(row_ptr[s + 1]) - a;
+        if (lane == 0) p_d = d;
+        // chunk c0 of the list: entry t - c0 is that of row(s)[t], of the root
+        // for t == d
+        auto entries = [&](int c0, int first) {
+            for (int k = first; k < nt && c0 + k <= d; k += SDNR_WAVE) {
+                const int t = c0 + k;
+                p_col[k] = t < d ? col[a + t] : s;
+                fold_encode(fmt, hbytes, s, t < d ? port[a + t] : -1, t < d ? t : 63,
+                            t < d ? 1 : 0, &p_w0[k], &p_w1[k], &p_wh[k]);
             }
+        };
+        // second trip: row(s), a lane per entry, and the parent's row bounds
+        int av = -1, aprt = -1;
+        if (lane < d) {
+            av = col[a + lane];
+            aprt = port[a + lane];
         }
+        const int par = fmt == kTreeInt32 ? (int)e
+                        : e == 0xFFFFFFFFu ? -1
+                        : (int)(e & (fmt == kTreePort16 ? 0xFFFFu : 0x3FFFFFFu));
+        int lo = 0, n = 0;
+        if (par >= 0) {
+            lo = row_ptr[par];
+            n = row_ptr[par + 1] - lo;
+        }
+        // third trip: the parent's row, a lane per entry
+        int cv = -1, cprt = -1;
+        if (lane < n) {
+            cv = col[lo + lane];
+            cprt = port[lo + lane];
+        }
+        if (lane <= d) {
+            p_col[lane] = lane < d ? av : s;
+            fold_encode(fmt, hbytes, s, aprt, lane < d ? lane : 63, lane < d ? 1 : 0, &p_w0[lane],
+                        &p_w1[lane], &p_wh[lane]);
+        }
+        entries(0, lane + SDNR_WAVE);            // what a lane per entry has not covered
+        // the entry of ls comes last in the first chunk, written by the lane
+        // that found it (none: no entry)
+        int bv = -1, bpar = -1, bprt = -1, bslot = 63, bhop = -1;
+        if (par < 0) {
+            if (lane == 0) bv = ls;
+        } else {
+            if (lane < n && cv == ls) {
+                bv = ls;
+                bpar = par;
+                bprt = cprt;
+                bslot = lane;
+                bhop = hop;
+            }
+            for (int k = lane + SDNR_WAVE; k < n; k += SDNR_WAVE)
+                if (col[lo + k] == ls) {
+                    bv = ls;
+                    bpar = par;
+                    bprt = port[lo + k];
+                    bslot = k;
+                    bhop = hop;
+                }
+        }
+        const int nb = d < nt ? d + 1 : nt;
+        const uint64_t fm = __ballot(bv >= 0);
+        if (lane == (fm ? __ffsll((unsigned long long)fm) - 1 : 0)) {
+            p_col[nb] = bv;
+            fold_encode(fmt, hbytes, bpar, bprt, bslot, bhop, &p_w0[nb], &p_w1[nb], &p_wh[nb]);
+        }
+        fold_lds_barrier();                      // the list is complete
+        for (int c0 = nt; c0 <= d; c0 += nt) {   // a row wider than the workgroup
+            fold_lds_barrier();                  // the owners are done with the last chunk
+            entries(c0, lane);
+            fold_lds_barrier();
+        }
+        return;
     }
     fold_copy_row(L < 0 ? nullptr : reinterpret_cast<const char *>(in0 + lb),
                   reinterpret_cast<char *>(out0 + ob), 4 * (size_t)V, 4, (vec & 1) != 0);
@@ -3391,12 +3508,32 @@ __global__ __launch_bounds__(kFoldDeriveThreads) void dfs_fold_derive_kernel(
         fold_copy_row(L < 0 ? nullptr : inh + lb * hbytes, outh + ob * hbytes,
                       (size_t)hbytes * V, hbytes, (vec & 4) != 0);
     if (!patch) return;
-    __syncthreads();
-    if (av >= 0) fold_put(fmt, hbytes, out0, out1, outh, ob + av, apar, aprt, aslot, ahop);
-    if (bv >= 0) fold_put(fmt, hbytes, out0, out1, outh, ob + bv, bpar, bprt, bslot, bhop);
-    for (int t = tid + kFoldDeriveThreads; t <= d; t += kFoldDeriveThreads) {   // rows wider than the workgroup
-        if (t < d) fold_put(fmt, hbytes, out0, out1, outh, ob + col[a + t], s, port[a + t], t, 1);
-        else fold_put(fmt, hbytes, out0, out1, outh, ob + s, s, -1, 63, 0);
+    // the patch stores below follow this wave's copy stores in issue order,
+    // whichever of its lanes stores: wavefront scope, no instruction
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    // the owner of a word by its table's copy form
+    const int sh0 = (vec & 1) ? 2 : 0, sh1 = (vec & 2) ? 2 : 0,
+              shh = (vec & 4) ? (hbytes == 2 ? 3 : 2) : 0;
+    fold_lds_barrier();
+    const int d = uniform(p_d);
+    for (int c0 = 0; c0 <= d; c0 += nt) {
+        if (c0) {
+            fold_lds_barrier();
+            fold_lds_barrier();
+        }
+        const int left = d + 1 - c0;
+        const int nent = (left < nt ? left : nt) + (c0 ? 0 : 1);
+        for (int e0 = 0; e0 < nent; e0 += SDNR_WAVE) {
+            const int k = e0 + lane;
+            const int x = k < nent ? p_col[k] : -1;
+            fold_apply(x, k < nent ? p_w0[k] : 0u, sh0, reinterpret_cast<fold_u32 *>(out0 + ob));
+            if (fmt == kTreeInt32)
+                fold_apply(x, k < nent ? p_w1[k] : 0u, sh1, reinterpret_cast<fold_u32 *>(out1 + ob));
+            if (hbytes == 2)
+                fold_apply(x, k < nent ? p_wh[k] : 0u, shh, reinterpret_cast<fold_u16 *>(outh) + ob);
+            else if (hbytes == 4)
+                fold_apply(x, k < nent ? p_wh[k] : 0u, shh, reinterpret_cast<fold_u32 *>(outh) + ob);
+        }
     }
 }
 
@@ -3551,7 +3688,7 @@ int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
                     (!packed && vec_ok(d_port, 4 * (size_t)V) ? 2 : 0) |
                     (hbytes && vec_ok(d_hops, (size_t)hbytes * V) ? 4 : 0);
     const int fmt = packed ? (slots ? kTreeSlot : kTreePort16) : kTreeInt32;
-    hipLaunchKernelGGL(dfs_fold_derive_kernel, dim3(nsrc), dim3(kFoldDeriveThreads), 0,
+    hipLaunchKernelGGL(dfs_fold_derive_kernel, dim3(nsrc), dim3(kFoldDeriveThreads + SDNR_WAVE), 0,
                        ctx->stream, V, fmt, hbytes, vec, d_src, lsrc, lead, ctx->row_ptr,
                        ctx->col, ctx->port, reinterpret_cast<const uint32_t *>(t0), o0,
                        reinterpret_cast<const uint32_t *>(t1), reinterpret_cast<uint32_t *>(d_port),
