@@ -653,6 +653,69 @@ int sdnr_widest_tables(sdnr_ctx *ctx, const uint32_t *pcost, const uint32_t *uti
                        const int32_t *dst, int32_t ndst, uint32_t *bott, int32_t *nh,
                        int32_t *nh_port, uint32_t flags);
 
+/* Max-min fair rates of flows routed over single-path route tables: what each
+ * pair gets when the flows share the links the way TCP or RoCE flows
+ * approximately do, the link that limits it, and every link's carried rate.
+ * A flow i is a pair of sdnr_link_loads -- row r of tree (same layouts, same
+ * pair_off), vertex verts[i] -- with a multiplicity mult[i] (u64: that many
+ * identical parallel flows; 0: absent; mult NULL: all 1; the caller keeps the
+ * sum below 2^53) and up to two extra constraints extra[2*i], extra[2*i+1]:
+ * indices in [E, E + nextra) into cap, -1 for none (extra NULL: none; e.g. the
+ * two hosts' ports).  Its links are the tree links from verts[i] to the row's
+ * root.  cap [E + nextra] holds positive finite doubles: the links' capacities
+ * in the uploaded CSR's edge order, then the extras'.
+ * Progressive filling, with rem = cap, used = 0, n_prev = 0, every flow alive;
+ * round k = 0, 1, ...:
+ *   1. n[e] = sum of mult over the alive flows that cross e (u64, exact);
+ *   2. for k > 0: m = n_prev[e] - n[e], p = r_{k-1} * (double)m, used[e] += p,
+ *      rem[e] = max(rem[e] - p, 0.0) -- the multiply, the add and the subtract
+ *      each rounded on its own (no FMA);
+ *   3. share[e] = rem[e] / n[e] where n[e] > 0, else +inf; r_k = min share;
+ *      r_k == +inf ends the rounds;
+ *   4. e is saturated iff share[e] == r_k; every alive flow that crosses a
+ *      saturated link or extra gets rate r_k, round k and bott = the first
+ *      saturated tree link walking from verts[i] toward the root, else
+ *      extra[2*i] if saturated, else extra[2*i+1], and is dead; n_prev = n.
+ * One more step 2 after the last round makes used final.  Every round kills a
+ * flow, so there are at most min(flows, E + nextra) rounds.  The allocation is
+ * the max-min fair one, which is unique; every step is deterministic, so the
+ * results are bit-exact and repeatable (engine.fair_rates_host restates them).
+ *   rate  [npairs] f64, bott [npairs] i32 (an index into cap), round [npairs]
+ *         i32, at the flows' indices: WRITTEN for pair_off[0] .. pair_off[nrows];
+ *   level [max_rounds] f64: level[k] = r_k, +inf from *nrounds on;
+ *   used  [E + nextra] f64: the rate every link and extra carries;
+ *   nrounds  HOST int32: the rounds run, written before the call returns.
+ * A flow at the row's root (no link) without an extra: rate +inf, round -1,
+ * bott -1.  A vertex outside [0, V) or unreached in its row, a multiplicity 0,
+ * and every flow of a rejected row: rate 0.0, round -1, bott -1.  A vertex is
+ * a root when it is its own parent; SDNR_LOADS_TO_ROOT rows (next-hop rows,
+ * SDNR_TREE_INT32 only, the link is v -> nh[v]) hold -1 at the destination and
+ * at unreachable vertices alike, so there a vertex without a next hop is taken
+ * as the root: pass -1 as the vertex of a pair known to be unreachable.  If
+ * max_rounds rounds do not finish the filling, the flows still alive keep rate
+ * 0.0, bott -1 and round -2 and *nrounds is max_rounds.
+ * Device pointers only (flags must hold SDNR_DEVICE_PTRS).  No grid-wide
+ * barrier: a round is two launches on the context's stream (a row kernel in
+ * sdnr_link_loads' shape -- sdnr_last_kernel names its form,
+ * "fair_rows_kernel<lds>" or "fair_rows_kernel<global>" -- and a kernel over
+ * the E + nextra entries); rounds are queued in batches and the call waits for
+ * an 8-byte status word per batch, so it returns when the rounds are done
+ * (rate, bott, round and used are final then; level after sdnr_synchronize).
+ * sdnr_last_launches gives the launches of the call.  On a multi-device
+ * context it runs on the primary device.  nrows == 0 or no pairs: SDNR_OK,
+ * *nrounds = 0, nothing else touched.  pair_off[0] > pair_off[nrows] is
+ * SDNR_ERR_INVAL at once.  A row that is not a tree of the graph (every vertex
+ * with a parent must have that link), offsets of a row outside the pair list,
+ * a capacity that is not positive and finite (taken as +inf) and an extra
+ * outside [E, E + nextra) (ignored) are reported by sdnr_synchronize as
+ * SDNR_ERR_INVAL; the doublings are bounded and such a row adds nothing. */
+int sdnr_fair_rates(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nrows,
+                    const int64_t *pair_off, const int32_t *verts, const uint64_t *mult,
+                    const int32_t *extra /* [npairs][2] or NULL */, const double *cap,
+                    int32_t nextra, double *rate, int32_t *bott, int32_t *round,
+                    double *level, int32_t max_rounds, double *used,
+                    int32_t *nrounds /* host */, uint32_t flags);
+
 /* Flood ports (TopologyManager._is_edge_port / _do_broadcast, reference
  * sdnmpi/topology.py:150-177): is_edge[i] = 1 iff ports[i] is neither end of
  * any link.  Keys are (dense switch id << 32) | port_no; ends (both ends of

@@ -261,6 +261,18 @@ constexpr int kWidestLdsMaxV6 = 3333;
 constexpr int kWidestLdsMaxV4 = 5000;
 constexpr int kWidestLdsMaxV = 10000;
 
+constexpr int kErrFairRates = 1048576; // sdnr_fair_rates: a row is not a tree of the graph / bad offsets / a bad capacity or extra
+
+// sdnr_fair_rates keeps a row's subtree sums, ancestors and link indices in
+// LDS (two u64 and two u16 generations and one i32: 24 bytes per vertex; the
+// first-saturated-link search aliases the sums) up to this V -- what the CU's
+// LDS holds, rounded down to a hundred: 6,800, 163,200 of 163,840 bytes --,
+// else in global scratch (u32 ancestors: 28 bytes per vertex and workgroup, at
+// most kLoadsScratchBytes in all)
+constexpr int kFairBytesPerV = 24;
+constexpr int kFairLdsMaxV = SDNR_LDS_PER_CU / kFairBytesPerV / 100 * 100;
+static_assert(kFairLdsMaxV == 6800 && kFairLdsMaxV < 0xFFFF, "ancestors in LDS are u16");
+
 // error plumbing (capi.hip)
 int sdnr_fail(int code, const char *fmt, ...);
 int sdnr_hip_fail(hipError_t e, const char *what);
@@ -371,5 +383,13 @@ int sdnr_launch_lfa_tables(sdnr_ctx *ctx, const uint32_t *d_pcost_all, const int
 int sdnr_launch_widest_tables(sdnr_ctx *ctx, const uint32_t *d_pcost, const uint32_t *d_util,
                               const int32_t *d_dst, int32_t ndst, uint32_t *d_bott, int32_t *d_nh,
                               int32_t *d_nh_port);
+// max-min fair rates of flows routed over tree rows (fair_rates.hip); waits for
+// the rounds and writes *nrounds
+int sdnr_launch_fair_rates(sdnr_ctx *ctx, const void *d_tree, int32_t layout, bool to_root,
+                           int32_t nrows, const int64_t *d_pair_off, int64_t pair_lo,
+                           int64_t pair_hi, const int32_t *d_verts, const uint64_t *d_mult,
+                           const int32_t *d_extra, const double *d_cap, int32_t nextra,
+                           double *d_rate, int32_t *d_bott, int32_t *d_round, double *d_level,
+                           int32_t max_rounds, double *d_used, int32_t *nrounds);
 int sdnr_launch_edge_ports(sdnr_ctx *ctx, const uint64_t *d_ends, int32_t nends,
                            const uint64_t *d_ports, int32_t nports, uint8_t *d_is_edge);

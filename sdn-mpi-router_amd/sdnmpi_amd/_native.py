@@ -52,7 +52,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_cost_ecmp_link_loads", "sdnr_graph_twin_reps", "sdnr_last_dfs_searched",
     "sdnr_last_dfs_form",
     "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables", "sdnr_whatif_ecmp_link_loads",
-    "sdnr_widest_tables",
+    "sdnr_widest_tables", "sdnr_fair_rates",
 )
 
 
@@ -119,6 +119,8 @@ def _bind(L):
         "sdnr_whatif_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp,
                                          vp, vp, u32], c_int),
         "sdnr_widest_tables": ([vp, vp, vp, vp, i32, vp, vp, vp, u32], c_int),
+        "sdnr_fair_rates": ([vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp,
+                             ctypes.POINTER(i32), u32], c_int),
         "sdnr_graph_twin_reps": ([vp, vp], c_int),
         "sdnr_last_dfs_searched": ([vp, ctypes.POINTER(i32)], c_int),
         "sdnr_last_dfs_form": ([vp, ctypes.POINTER(i32)], c_int),
@@ -665,6 +667,25 @@ class Context(object):
         _check(self._lib.sdnr_widest_tables(
             self._h, p(pcost_ptr), p(util_ptr), p(dst_ptr), int(ndst), p(bott_ptr), p(nh_ptr),
             p(nh_port_ptr), flags))
+
+    def fair_rates_device(self, tree_ptr, layout, nrows, pair_off_ptr, verts_ptr, mult_ptr,
+                          extra_ptr, cap_ptr, nextra, rate_ptr, bott_ptr, round_ptr, level_ptr,
+                          max_rounds, used_ptr, to_root=False, timing=False):
+        """Max-min fair rates of flows routed over [nrows][V] tree rows
+        (sdnr_fair_rates, device pointers): writes rate (f64), bott and round
+        (i32) per flow, level (f64 [max_rounds]) and used (f64 [E + nextra]),
+        and returns the number of rounds.  ``mult_ptr`` 0: every flow counts
+        once; ``extra_ptr`` 0: no extra constraints; ``to_root``: next-hop
+        rows (SDNR_LOADS_TO_ROOT).  Waits for the rounds; errors of the rows
+        surface in ``synchronize``."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_TO_ROOT if to_root else 0)
+        p = lambda a: ctypes.c_void_p(a) if a else None    # noqa: E731
+        n = ctypes.c_int32()
+        _check(self._lib.sdnr_fair_rates(
+            self._h, p(tree_ptr), int(layout), int(nrows), p(pair_off_ptr), p(verts_ptr),
+            p(mult_ptr), p(extra_ptr), p(cap_ptr), int(nextra), p(rate_ptr), p(bott_ptr),
+            p(round_ptr), p(level_ptr), int(max_rounds), p(used_ptr), ctypes.byref(n), flags))
+        return n.value
 
     def apsp_device(self, dist_ptr, timing=False):
         flags = DEVICE_PTRS | (TIMING if timing else 0)

@@ -48,7 +48,8 @@ __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "failure_ecmp_link_loads_host", "normalise_cost_scenarios",
            "whatif_ecmp_link_loads_host", "peak_utilisation", "lfa_tables_host", "LFA_MAX_V", "LFA_BACKUP",
            "LFA_DOWNSTREAM", "LFA_NODE", "widest_tables_host", "check_link_utilisation", "UTIL_MAX",
-           "WIDEST_LDS_MAX_V", "WIDEST_LDS_B4_MAX_V", "WIDEST_LDS_B6_MAX_V"]
+           "WIDEST_LDS_MAX_V", "WIDEST_LDS_B4_MAX_V", "WIDEST_LDS_B6_MAX_V", "fair_rates_host",
+           "check_fair_flows", "FAIR_LDS_MAX_V", "FAIR_MULT_LIMIT"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -335,6 +336,172 @@ def link_loads_host(csr, tree, layout, rows, dsts, weights=None, to_root=False):
         raise ValueError("link_loads_host: a tree link the graph does not have")
     np.add.at(load, e, acc[r, v])
     return load
+
+
+FAIR_LDS_MAX_V = 6800           # csrc/common.h kFairLdsMaxV: fair-rate row state in LDS up to this V
+FAIR_MULT_LIMIT = 1 << 53       # the multiplicities of one call sum below this: doubles hold them
+
+
+def check_fair_flows(E, n, mult, cap, extra):
+    """(mult uint64 [n], cap float64 [E + nextra], extra int64 [n, 2], nextra)
+    after sdnr_fair_rates' checks, done on the host where they can name the
+    culprit: capacities positive and finite, extras -1 or in [E, E + nextra),
+    multiplicities summing below 2**53."""
+    cap = np.ascontiguousarray(np.asarray(cap, np.float64).reshape(-1))
+    if cap.shape[0] < E:
+        raise ValueError("fair rates: %d capacities for %d links" % (cap.shape[0], E))
+    if not bool((np.isfinite(cap) & (cap > 0)).all()):
+        raise ValueError("fair rates: capacities must be positive finite numbers")
+    nextra = cap.shape[0] - E
+    if mult is None:
+        mult = np.ones(n, np.uint64)
+    else:
+        mult = np.ascontiguousarray(np.asarray(mult, np.uint64).reshape(-1))
+        if mult.shape[0] != n:
+            raise ValueError("fair rates: %d multiplicities for %d flows" % (mult.shape[0], n))
+    # (a u64 sum could wrap: the halves are summed apart)
+    if (int((mult >> np.uint64(32)).sum()) << 32) + int((mult & np.uint64(0xFFFFFFFF)).sum()) \
+            >= FAIR_MULT_LIMIT:
+        raise ValueError("fair rates: the multiplicities must sum below 2**53")
+    if extra is None:
+        extra = np.full((n, 2), -1, np.int64)
+    else:
+        extra = np.asarray(extra, np.int64).reshape(n, 2)
+        if not bool(((extra == -1) | ((extra >= E) & (extra < E + nextra))).all()):
+            raise ValueError("fair rates: an extra constraint outside [E, E + nextra)")
+    return mult, cap, extra, nextra
+
+
+def fair_rates_host(csr, tree, layout, rows, verts, mult, cap, extra=None, to_root=False):
+    """numpy restatement of sdnr_fair_rates (the CPU tests' engine double and
+    the checker of fair_rates.hip): max-min fair rates by progressive filling
+    of flows (row ``rows[i]`` of ``tree``, vertex ``verts[i]``, multiplicity
+    ``mult[i]`` or 1, extra constraints ``extra[i]`` -- two indices in [E, E +
+    nextra) into ``cap`` or -1).  Returns ``(rate float64 [n], bott int32 [n],
+    round int32 [n], level float64 [rounds], used float64 [E + nextra])``.
+
+    The definition is sdnroute.h's, step for step: exact u64 counts, then per
+    link and round one multiply, one add, one subtract and one divide, each a
+    separate numpy operation (numpy does not fuse them), so the device results
+    are these bit for bit.  Every used row is laid out once -- parents, links
+    toward the root, and the ancestor tables J, J o J, ... of pointer jumping
+    --; a round is then a handful of whole-table gathers and scatters whatever
+    the depth of the trees.  A flow at the row's root without an extra reads
+    +inf / -1 / -1; a vertex outside [0, V) or unreached in its row and a
+    multiplicity 0 read 0.0 / -1 / -1.  In ``to_root`` rows a vertex without a
+    next hop is taken as the root (pass -1 for a pair known to be unreachable).
+    A row that is no tree of the graph raises ValueError."""
+    V, E = int(csr.V), int(csr.E)
+    rows = np.asarray(rows, np.int64).reshape(-1)
+    verts = np.asarray(verts, np.int64).reshape(-1)
+    n = rows.shape[0]
+    mult, cap, extra, nextra = check_fair_flows(E, n, mult, cap, extra)
+    NE = E + nextra
+    rate = np.zeros(n, np.float64)
+    bott = np.full(n, -1, np.int32)
+    rnd = np.full(n, -1, np.int32)
+    used = np.zeros(NE, np.float64)
+    if n == 0:
+        return rate, bott, rnd, np.zeros(0, np.float64), used
+    urows, rix = np.unique(rows, return_inverse=True)
+    words = np.asarray(tree)[urows]
+    par = words.astype(np.int64) if layout == INT32 else tree_parent(words, layout)
+    R = par.shape[0]
+    vid = np.broadcast_to(np.arange(V, dtype=np.int64), par.shape)
+    own = par == vid
+    root = own | (par < 0) if to_root else own
+    par = np.where((par < 0) | own, -1, par)
+    if (par >= V).any():
+        raise ValueError("fair_rates_host: a parent that is no vertex")
+    has = par >= 0
+    # the link of v toward the root
+    ev = np.full(par.shape, -1, np.int64)
+    if has.any():
+        keys, _ = _edge_keys_host(csr)
+        r, v = np.nonzero(has)
+        p = par[r, v]
+        k = (v * V + p) if to_root else (p * V + v)
+        e = np.minimum(np.searchsorted(keys, k), max(E - 1, 0))
+        if E == 0 or not np.array_equal(keys[e], k):
+            raise ValueError("fair_rates_host: a tree link the graph does not have")
+        ev[r, v] = e
+    # flat tables: entry r * V + v; J_0 = parent, J_{j+1} = J_j o J_j
+    base = (np.arange(R, dtype=np.int64) * V)[:, None]
+    jump = np.where(has, par + base, -1).ravel()
+    ev, has, root = ev.ravel(), has.ravel(), root.ravel()
+    chain = []
+    for _ in range(max(1, V).bit_length() + 1):
+        ok = jump >= 0
+        if not ok.any():
+            break
+        src = np.nonzero(ok)[0]
+        chain.append((jump, src, jump[src]))
+        nxt = np.full_like(jump, -1)
+        nxt[src] = jump[jump[src]]
+        jump = nxt
+    else:
+        raise ValueError("fair_rates_host: a row is not a tree")
+
+    inside = (verts >= 0) & (verts < V)
+    at = rix.reshape(-1) * V + np.where(inside, verts, 0)
+    x0, x1 = extra[:, 0], extra[:, 1]
+    there = inside & (mult > 0) & (has[at] | root[at])
+    bare = there & ~has[at] & (x0 < 0) & (x1 < 0)
+    rate[bare] = np.inf
+    alive = there & ~bare
+
+    rem = cap.copy()
+    n_prev = np.zeros(NE, np.uint64)
+    level = []
+    r_prev = 0.0
+    inf = np.float64(np.inf)
+    for k in range(n + 2):
+        # 1. the alive multiplicity that crosses every link and extra
+        a = np.nonzero(alive)[0]
+        A = np.zeros(R * V, np.uint64)
+        np.add.at(A, at[a], mult[a])
+        for _, src, dst in chain:
+            nxt = A.copy()
+            np.add.at(nxt, dst, A[src])
+            A = nxt
+        cnt = np.zeros(NE, np.uint64)
+        sel = np.nonzero(has & (A != 0))[0]
+        np.add.at(cnt, ev[sel], A[sel])
+        a0 = a[x0[a] >= 0]
+        np.add.at(cnt, x0[a0], mult[a0])
+        a1 = a[(x1[a] >= 0) & (x1[a] != x0[a])]
+        np.add.at(cnt, x1[a1], mult[a1])
+        # 2. what the flows frozen last round carry
+        if k > 0:
+            p = r_prev * (n_prev - cnt).astype(np.float64)
+            used = used + p
+            rem = np.maximum(rem - p, 0.0)
+        # 3. the next level
+        share = np.full(NE, inf)
+        np.divide(rem, cnt.astype(np.float64), out=share, where=cnt != 0)
+        r = share.min() if NE else inf
+        if r == inf:
+            break
+        level.append(r)
+        # 4. the first saturated link toward the root, else a saturated extra
+        B = np.where(has & (share[np.where(has, ev, 0)] == r), ev, -1)
+        for jump, _, _ in chain:
+            ok = (B < 0) & (jump >= 0)
+            B = np.where(ok, B[np.where(ok, jump, 0)], B)
+        b = B[at[a]]
+        e0, e1 = x0[a], x1[a]
+        s0 = (e0 >= 0) & (share[np.where(e0 >= 0, e0, 0)] == r)
+        s1 = (e1 >= 0) & (share[np.where(e1 >= 0, e1, 0)] == r)
+        b = np.where(b >= 0, b, np.where(s0, e0, np.where(s1, e1, -1)))
+        hit = a[b >= 0]
+        rate[hit] = r
+        rnd[hit] = k
+        bott[hit] = b[b >= 0]
+        alive[hit] = False
+        n_prev, r_prev = cnt, r
+    else:
+        raise AssertionError("fair_rates_host: a round froze no flow")
+    return rate, bott, rnd, np.asarray(level, np.float64), used
 
 
 SPLITS = ("route", "hop")
@@ -1239,6 +1406,77 @@ class RouteEngine(object):
                                    to_root=to_root, timing=timing)
         self.ctx.synchronize()              # raises if a row was not a tree
         return load.cpu().numpy().view(np.uint64)
+
+    def fair_rates(self, export, tree, layout, rows, verts, mult=None, cap=None, extra=None,
+                   to_root=False, timing=False):
+        """Max-min fair rates of flows routed over device tree rows
+        (fair_rates.hip, sdnr_fair_rates): ``(rate float64 [n], bott int32 [n],
+        round int32 [n], level float64 [rounds], used float64 [E + nextra])``
+        in the flows' order, bit for bit what ``fair_rates_host`` returns.
+
+        ``tree``, ``layout``, ``rows``, ``to_root`` as in ``link_loads``; flow
+        i sits at dense switch ``verts[i]`` of row ``rows[i]``, counts
+        ``mult[i]`` times (u64, None: once; the sum stays below 2**53) and is
+        also bound by ``extra[i]``: two indices in [E, E + nextra) into
+        ``cap``, -1 for none (None: no extras).  ``cap``: float64 [E + nextra]
+        positive finite capacities, the links' in the CSR's edge order first
+        (None: 1.0 per link, no extras).  The flows are sorted by row here and
+        every row stays on the device across the rounds."""
+        self.load(export)
+        t = self._torch
+        V, E = int(export.csr.V), int(export.csr.E)
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        n = rows.shape[0]
+        if cap is None:
+            cap = np.ones(E, np.float64)
+        mult_in = mult
+        mult, cap, extra_all, nextra = check_fair_flows(E, n, mult, cap, extra)
+        NE = E + nextra
+        nrows = int(tree.shape[0])
+        if n == 0 or nrows == 0:
+            if n:
+                raise ValueError("fair_rates: a pair names a row outside the table")
+            return (np.zeros(0, np.float64), np.zeros(0, np.int32), np.zeros(0, np.int32),
+                    np.zeros(0, np.float64), np.zeros(NE, np.float64))
+        if rows.min() < 0 or rows.max() >= nrows:
+            raise ValueError("fair_rates: a pair names a row outside the table")
+        order, off = _pairs_by_row(rows, nrows)
+        x = np.asarray(verts, np.int64).reshape(-1)[order]
+        x = np.where((x < 0) | (x >= V), -1, x).astype(np.int32)
+        tree = tree.contiguous()
+        d_off = t.from_numpy(off).to(self.dev)
+        d_x = t.from_numpy(x).to(self.dev)
+        d_m = d_e = None
+        if mult_in is not None:
+            d_m = t.from_numpy(np.ascontiguousarray(mult[order]).view(np.int64)).to(self.dev)
+        if extra is not None:
+            d_e = t.from_numpy(np.ascontiguousarray(extra_all[order].astype(np.int32))).to(self.dev)
+        d_cap = t.from_numpy(cap).to(self.dev)
+        max_rounds = min(n, NE)
+        rate = t.empty(n, dtype=t.float64, device=self.dev)
+        bott = t.empty(n, dtype=t.int32, device=self.dev)
+        rnd = t.empty(n, dtype=t.int32, device=self.dev)
+        level = t.empty(max_rounds, dtype=t.float64, device=self.dev)
+        used = t.zeros(NE, dtype=t.float64, device=self.dev)
+        lay = {PORT16: _native.TREE_PORT16, SLOT: _native.TREE_SLOT,
+               INT32: _native.TREE_INT32}[layout]
+        self._ready()
+        rounds = self.ctx.fair_rates_device(
+            tree.data_ptr(), lay, nrows, d_off.data_ptr(), d_x.data_ptr(),
+            d_m.data_ptr() if d_m is not None else 0, d_e.data_ptr() if d_e is not None else 0,
+            d_cap.data_ptr() if NE else 0, nextra, rate.data_ptr(), bott.data_ptr(),
+            rnd.data_ptr(), level.data_ptr() if max_rounds else 0, max_rounds,
+            used.data_ptr() if NE else 0, to_root=to_root, timing=timing)
+        self.ctx.synchronize()              # raises if a row was not a tree
+        out = []
+        for a in (rate, bott, rnd):
+            a = a.cpu().numpy()
+            if not isinstance(order, slice):
+                back = np.empty_like(a)
+                back[order] = a
+                a = back
+            out.append(a)
+        return out[0], out[1], out[2], level.cpu().numpy()[:rounds], used.cpu().numpy()
 
     def ecmp_link_loads(self, export, dist, rows, srcs, weights=None, split="route",
                         timing=False):

@@ -26,7 +26,7 @@ first route query raises (``sdnmpi_amd._native.NativeUnavailable`` /
 
 import numpy as np
 
-from ..engine import (COST_INF, COST_MAX, DEFAULT_TABLE_BUDGET, INT32, LFA_MAX_V, UTIL_MAX, RouteEngine, TableCache, _gather,
+from ..engine import (COST_INF, COST_MAX, DEFAULT_TABLE_BUDGET, FAIR_MULT_LIMIT, INT32, LFA_MAX_V, UTIL_MAX, RouteEngine, TableCache, _gather,
                       _host, _take, _torch, _u16, check_link_costs, least_cost_paths_lex,
                       peak_utilisation,
                       shortest_paths_lex, tree_path)
@@ -39,7 +39,7 @@ except Exception:   # noqa: BLE001 - Ryu is not a dependency of the engine
     OFPP_LOCAL = 0xfffe
 
 __all__ = ["TopologyDB", "LinkLoads", "SplitLinkLoads", "FailureLoads", "CostChangeLoads",
-           "CostTuning", "Admission", "OFPP_LOCAL",
+           "CostTuning", "Admission", "FairRates", "OFPP_LOCAL",
            "sdn_mpi_mac"]
 
 _INF = 0xFFFF
@@ -232,6 +232,81 @@ class Admission(object):
 
 
 CAPACITY_MAX = 1 << 53            # admit_flows: load * 1024 // capacity stays in 64 bits
+
+
+class FairRates(object):
+    """Predicted max-min fair throughput (:meth:`TopologyDB.fair_rates`).
+
+    Per input pair, in the order given: ``pairs``, ``weights`` (uint64
+    multiplicities), ``rate`` (float64: what ONE flow of the pair gets, in the
+    capacities' unit; ``inf`` for a pair that crosses nothing modelled),
+    ``routed`` (bool: unknown hosts and unreachable pairs are False and have
+    rate 0.0), ``round`` (int32: the filling round that froze the pair, -1
+    where none did) and ``bottleneck`` (the link that limits the pair as
+    ``(src_dpid, dst_dpid)``, a host port as ``("host", mac)``, or None).
+    ``levels`` are the rates of the rounds, ascending, ``rounds`` their number;
+    ``link_rate`` is a :class:`SplitLinkLoads` of the rate every link carries
+    (last hops: the rate out of every host port, when host ports are
+    modelled).  An MPI result also has ``bytes`` and ``time`` per pair."""
+
+    #: a link counts as saturated when its spare capacity is below this share
+    SATURATED = 1e-9
+
+    def __init__(self, pairs, weights, rate, routed, rnd, bottleneck, levels, link_rate, cap,
+                 used, names):
+        self.pairs = pairs
+        self.weights = weights
+        self.rate = rate
+        self.routed = routed
+        self.round = rnd
+        self.bottleneck = bottleneck
+        self.levels = levels
+        self.rounds = int(levels.shape[0])
+        self.link_rate = link_rate
+        self._cap, self._used, self._names = cap, used, names
+        self.bytes = None
+        self.time = None
+
+    def saturated_links(self):
+        """The links, as ``(src_dpid, dst_dpid)``, and host ports, as
+        ``("host", mac)``, that are full: spare capacity below ``SATURATED``
+        (1e-9) of the capacity, the rounding of the rounds' sums allowed for."""
+        full = np.nonzero(self._cap - self._used <= self.SATURATED * self._cap)[0]
+        out = []
+        for e in full.tolist():
+            x = self._names(e)
+            if x not in out:
+                out.append(x)
+        return out
+
+    @property
+    def min_rate(self):
+        """The smallest rate of a routed pair of nonzero weight (``levels[0]``
+        when a round ran; ``inf`` when nothing is constrained; None without
+        such a pair)."""
+        ok = self.routed & (self.weights != 0)
+        return float(self.rate[ok].min()) if ok.any() else None
+
+    def slowest(self):
+        """The pairs frozen in round 0: those at ``levels[0]``, the job's
+        slowest flows."""
+        return [self.pairs[i] for i in np.nonzero(self.round == 0)[0].tolist()]
+
+    @property
+    def total(self):
+        """Sum of rate * weight over the routed pairs of finite rate: the
+        fabric's aggregate throughput under this traffic."""
+        ok = self.routed & np.isfinite(self.rate)
+        return float((self.rate[ok] * self.weights[ok].astype(np.float64)).sum())
+
+    def step_time(self):
+        """The largest ``time`` (MPI results): how long the exchange takes if
+        every pair kept its rate throughout -- an upper estimate, since flows
+        that finish early leave their share to the others.  ``inf`` when a
+        pair with bytes to send is not routed; 0.0 without pairs."""
+        if self.time is None:
+            raise ValueError("step_time needs the bytes of mpi_fair_rates")
+        return float(self.time.max()) if self.time.size else 0.0
 
 
 def _weights(weights, n):
@@ -2193,6 +2268,231 @@ class TopologyDB(object):
         :meth:`mpi_link_loads`)."""
         pairs, weights = self._rank_pairs(rank_to_mac, traffic)
         return self.tune_link_costs(pairs, weights, capacity, split, rounds, top, steps, apply)
+
+    # -- max-min fair rates ------------------------------------------------
+    FAIR_ROUTES = ("default", "shortest", "least_cost", "least_loaded")
+
+    def _fair_rows(self, ex, route, sv, dv):
+        """The single-path tables of ``route`` for switch pairs sv -> dv, all
+        of their rows resident at once: (tree, layout, rows, verts, to_root,
+        reach) as ``engine.fair_rates`` takes them -- per-source default trees
+        (row of sv, vertex dv) or per-destination next-hop rows (row of dv,
+        vertex sv); reach: the pairs that have a route.  The rounds revisit
+        every row, so a call is not chunked: rows beyond the table budget are
+        a ValueError."""
+        if route not in self.FAIR_ROUTES:
+            raise ValueError("route must be one of %s" % ", ".join(map(repr, self.FAIR_ROUTES)))
+        V = int(ex.csr.V)
+        budget = int(DEFAULT_TABLE_BUDGET if self._budget is None else self._budget)
+        c = self._cache
+        if route == "default":
+            key, other, store = sv, dv, c.dfs
+            room = max(1, store.cap() - 1) if store.row_bytes else 1 << 62
+        elif route == "shortest":
+            key, other, store = dv, sv, c.sp
+            room = max(1, store.cap() - 1) if store.row_bytes else 1 << 62
+            room = min(room, max(1, budget // max(1, 4 * V)))   # the rows are widened to int32
+        else:
+            key, other = dv, sv
+            room = self._cost_cap(ex) if route == "least_cost" else self._widest_cap(ex)
+        want = sorted(set(key.tolist()))
+        if len(want) > room:
+            raise ValueError("fair rates keep every table row of a call resident across the "
+                             "rounds: %d %s rows exceed the table budget of %d bytes (%d rows)"
+                             % (len(want), route, budget, room))
+        if route in ("default", "shortest"):
+            batch = self._host_vertices(ex) if self._batch else ()
+            get = c.sp_rows if route == "shortest" else c.dfs_rows
+            tabs = get(self.engine, want, batch)
+            slots = np.asarray([store.row[v] for v in key.tolist()], np.int64)
+            if route == "default":
+                # the hops plane holds -1 where unreached
+                reach = _gather(tabs[-1], slots, other) != -1
+                return tabs[0], c.layout, slots, other, False, reach
+            plane, nh = tabs[0], tabs[1]
+        else:
+            m = self._cost_rows(ex, want) if route == "least_cost" else self._widest_rows(ex, want)
+            slots = np.asarray([m["slot"][v] for v in key.tolist()], np.int64)
+            plane, nh = m["tabs"][0], m["tabs"][1]
+        # distances, costs and bottlenecks are held signed: no route reads -1
+        reach = _gather(plane, slots, other) != -1
+        urows, inv = np.unique(slots, return_inverse=True)
+        nh = _take(nh, urows)
+        if route == "shortest" and V <= 0xFFFF:
+            nh = _u16(nh)
+        nh = nh.astype(np.int32) if isinstance(nh, np.ndarray) else nh.to(dtype=_torch().int32)
+        return nh, INT32, inv.reshape(-1), other, True, reach
+
+    def _fair_capacity(self, ex, capacity):
+        """float64 [E] link capacities: None 1.0 each, a positive number for
+        every link, or a mapping as :meth:`_capacity_vector` takes it."""
+        E = int(ex.csr.E)
+        if capacity is None:
+            return np.ones(E, np.float64)
+        if isinstance(capacity, (int, float, np.integer, np.floating)) and \
+                not isinstance(capacity, bool):
+            if not (float(capacity) > 0 and np.isfinite(float(capacity))):
+                raise ValueError("capacity must be a positive finite number: %r" % (capacity,))
+            return np.full(E, float(capacity), np.float64)
+        return self._capacity_vector(ex, capacity)
+
+    def _fair(self, ex, pairs, w, sv, dv, ports, capacity, host_capacity, route):
+        """FairRates of pairs already resolved: dense switches sv -> dv (-1:
+        unknown host), multiplicities w, and per pair ``ports`` = (source
+        switch port, destination switch port, source MAC, destination MAC) for
+        the host-port constraints (None: not modelled)."""
+        n = sv.shape[0]
+        E, V = int(ex.csr.E), int(ex.csr.V)
+        if sum(int(x) for x in w.tolist()) >= FAIR_MULT_LIMIT:
+            raise ValueError("fair rates: the weights must sum below 2**53")
+        cap = self._fair_capacity(ex, capacity)
+        if host_capacity is not None:
+            if isinstance(host_capacity, bool) or \
+                    not isinstance(host_capacity, (int, float, np.integer, np.floating)) or \
+                    not (float(host_capacity) > 0 and np.isfinite(float(host_capacity))):
+                raise ValueError("host_capacity must be a positive finite number: %r"
+                                 % (host_capacity,))
+            if ports is None:
+                raise ValueError("host ports need MAC pairs")
+        ok = np.nonzero(sv >= 0)[0]
+        hkey = np.zeros((0, 2), np.int64)
+        nin = 0
+        macs = []
+        if host_capacity is None:
+            cols = np.stack([sv[ok], dv[ok]], 1).reshape(-1, 2)
+        else:
+            # extras: the ports into the fabric first, then the last hops
+            ikey, iinv = np.unique(np.stack([sv[ok], ports[0][ok]], 1).reshape(-1, 2), axis=0,
+                                   return_inverse=True)
+            hkey, hinv = np.unique(np.stack([dv[ok], ports[1][ok]], 1).reshape(-1, 2), axis=0,
+                                   return_inverse=True)
+            iinv, hinv = iinv.reshape(-1), hinv.reshape(-1)
+            nin = ikey.shape[0]
+            macs = [None] * (nin + hkey.shape[0])
+            for j, i in enumerate(ok.tolist()):
+                macs[iinv[j]] = macs[iinv[j]] or ports[2][i]
+                macs[nin + hinv[j]] = macs[nin + hinv[j]] or ports[3][i]
+            cols = np.stack([sv[ok], dv[ok], E + iinv, E + nin + hinv], 1).reshape(-1, 4)
+            cap = np.concatenate([cap, np.full(len(macs), float(host_capacity), np.float64)])
+        # pairs -> flows: equal (switches, extras) merge, multiplicities summed
+        fkey, finv = np.unique(cols, axis=0, return_inverse=True)
+        finv = finv.reshape(-1)
+        fw = np.zeros(fkey.shape[0], np.uint64)
+        np.add.at(fw, finv, w[ok])
+        rate = np.zeros(n, np.float64)
+        routed = np.zeros(n, bool)
+        rnd = np.full(n, -1, np.int32)
+        bott = np.full(n, -1, np.int64)
+        levels = np.zeros(0, np.float64)
+        used = np.zeros(cap.shape[0], np.float64)
+        if fkey.shape[0]:
+            fs, fd = fkey[:, 0], fkey[:, 1]
+            tree, layout, rows, verts, to_root, reach = self._fair_rows(ex, route, fs, fd)
+            # (next-hop rows cannot tell an unreached vertex from the root)
+            verts = np.where(reach, verts, -1)
+            extra = fkey[:, 2:4] if host_capacity is not None else None
+            r, b, k, levels, used = self.engine.fair_rates(ex, tree, layout, rows, verts, fw, cap,
+                                                           extra, to_root=to_root)
+            rate[ok], rnd[ok], bott[ok], routed[ok] = r[finv], k[finv], b[finv], reach[finv]
+        link = self._edge_links(ex)
+
+        def names(e):
+            return link(e) if e < E else ("host", macs[e - E])
+
+        bottleneck = [None if e < 0 else names(e) for e in bott.tolist()]
+        link_rate = self._link_loads_result(ex, used[:E], hkey, used[E + nin:], SplitLinkLoads)
+        return FairRates(pairs, w, rate, routed, rnd, bottleneck, levels, link_rate, cap, used,
+                         names)
+
+    def fair_rates(self, pairs, weights=None, capacity=None, host_capacity=None, route="default"):
+        """What every (src_mac, dst_mac) pair of ``pairs`` gets when all of
+        them send at once and share the links max-min fairly, as TCP or RoCE
+        (DCQCN) flows approximately do: the rate of each pair, the link that
+        limits it and the rate every link carries, as a :class:`FairRates`.
+        A link load says how much crosses a link; this says how fast.
+
+        ``route``: which single path a pair takes -- ``"default"``
+        (:meth:`find_route`), ``"shortest"`` (``find_route(multiple=True)[0]``),
+        ``"least_cost"`` (:meth:`find_route_least_cost`) or ``"least_loaded"``
+        (:meth:`find_route_least_loaded`).  ``weights``: multiplicities --
+        pair i stands for ``weights[i]`` identical parallel flows, each of
+        which gets ``rate[i]`` (non-negative ints, None: 1; 0: absent; the sum
+        must stay below 2**53, else ValueError).  ``capacity``: ``{(src_dpid,
+        dst_dpid): positive number}`` (links not named: 1.0), one positive
+        number for every link, or None: 1.0 each.  ``host_capacity`` None: the
+        host ports are not modelled and pairs between the same two switches
+        are one flow class; a positive number: every host port carries that
+        much in each direction, and a pair is also bound by its source host's
+        port into the fabric and by its last hop.
+
+        The allocation is the max-min fair one (progressive filling: raise
+        every rate together, freeze the flows of a link when it fills), which
+        is unique; the GPU runs the rounds (fair_rates.hip), bit for bit equal
+        to ``engine.fair_rates_host``.  Every table row the pairs need stays
+        resident across the rounds: more rows than the table budget holds are
+        a ValueError, not chunked.  Flows split over several routes (ECMP
+        fractions) are out of scope: every pair is on one path."""
+        ex = self.graph()
+        pairs = list(pairs)
+        n = len(pairs)
+        w = _weights(weights, n)
+        sv = np.full(n, -1, np.int64)
+        dv = np.full(n, -1, np.int64)
+        sport = np.zeros(n, np.int64)
+        dport = np.zeros(n, np.int64)
+        for i, (a, b) in enumerate(pairs):
+            ea, eb = self._endpoint(a), self._endpoint(b)
+            if ea is None or eb is None:
+                continue
+            sv[i] = ex.index[ea[0]]
+            dv[i] = ex.index[eb[0]]
+            sport[i] = self._last_hop(ea[0], ea[1], a)[1]
+            dport[i] = self._last_hop(eb[0], eb[1], b)[1]
+        ports = (sport, dport, [a for a, _ in pairs], [b for _, b in pairs])
+        return self._fair(ex, pairs, w, sv, dv, ports, capacity, host_capacity, route)
+
+    def all_pairs_fair_rates(self, capacity=None, route="default"):
+        """:meth:`fair_rates` of every ordered pair of distinct hosts at once
+        (all-to-all traffic), in the switch-pair form: ``pairs`` of the result
+        are ``(src_dpid, dst_dpid)`` over the host-bearing switches and
+        ``weights`` their host pairs, hosts(s) * (hosts(d) - [s == d]); host
+        ports are not modelled.  When a host MAC names a switch the MAC-pair
+        form is taken (``pairs`` are MAC pairs then), as in
+        :meth:`all_pairs_link_loads`."""
+        if any(self._mac_to_int(m) in self.switches for m in self.hosts):
+            macs = list(self.hosts)
+            return self.fair_rates([(a, b) for a in macs for b in macs if a != b], None, capacity,
+                                   None, route)
+        ex = self.graph()
+        hv = np.asarray(self._host_vertices(ex), np.int64)
+        hc = np.asarray(ex.host_count, np.int64)
+        n = hv.shape[0]
+        sv, dv = np.repeat(hv, n), np.tile(hv, n)
+        w = (hc[sv] * (hc[dv] - (sv == dv))).astype(np.uint64)
+        dp = ex.csr.dpids
+        pairs = list(zip(dp[sv].tolist(), dp[dv].tolist()))
+        return self._fair(ex, pairs, w, sv, dv, None, capacity, None, route)
+
+    def mpi_fair_rates(self, rank_to_mac, traffic=None, capacity=None, host_capacity=None,
+                       route="default"):
+        """:meth:`fair_rates` of an MPI job's exchange: the keys of ``traffic``
+        = {(src_rank, dst_rank): bytes} give the pairs, one flow each (None:
+        every ordered rank pair i != j, one byte each).  The result also has
+        ``bytes`` and ``time`` = bytes / rate per pair (``inf`` for bytes on a
+        pair without a route, 0.0 for no bytes), and ``step_time()``, the
+        largest: the exchange's duration if the rates held throughout -- flows
+        that finish early would leave their share to the rest, so the real
+        exchange is no slower than that."""
+        pairs, nbytes = self._rank_pairs(rank_to_mac, traffic)
+        res = self.fair_rates(pairs, None, capacity, host_capacity, route)
+        b = np.ones(len(pairs), np.float64) if nbytes is None else \
+            np.asarray([float(x) for x in nbytes], np.float64).reshape(-1)
+        if (b < 0).any():
+            raise ValueError("bytes are non-negative")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = np.where(b == 0, 0.0, b / res.rate)
+        res.bytes, res.time = b, t
+        return res
 
     def find_routes(self, pairs, multiple=False):
         """find_route over many (src_mac, dst_mac) pairs; tables are computed
