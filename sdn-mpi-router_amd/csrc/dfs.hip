@@ -3294,6 +3294,29 @@ __device__ __forceinline__ void fold_pin(uint16_t &v)
     v = (uint16_t)x;
 }
 
+// the derive kernel's stores, copy and patch stores alike, are write-through
+// (sc1): the row leaves the XCD's L2 for memory while the kernel still issues
+// stores, and the end-of-dispatch release finds no 13 MB of dirty lines to
+// write back before the next call's prep may start ("The
+// derive kernel's store policy"; plain, nt and sc0 sc1 stores measured there).
+// One policy for both kinds: a patch has to land behind the copy store of its
+// word by the wave's issue order alone
+typedef uint32_t __attribute__((ext_vector_type(4))) fold_v4;
+
+__device__ __forceinline__ void fold_store(uint4 *p, const uint4 &v)
+{
+    const fold_v4 w = {v.x, v.y, v.z, v.w};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(w) : "memory");
+}
+__device__ __forceinline__ void fold_store(fold_u32 *p, uint32_t v)
+{
+    asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
+}
+__device__ __forceinline__ void fold_store(fold_u16 *p, uint16_t v)
+{
+    asm volatile("global_store_short %0, %1, off sc1" : : "v"(p), "v"((uint32_t)v) : "memory");
+}
+
 // a row of n elements at out, a copy of the row at in (nullptr: every element
 // `ones`, an empty row in every layout): element k by thread k % threads
 template <typename T>
@@ -3302,7 +3325,7 @@ __device__ __forceinline__ void fold_copy_elems(const T *__restrict__ in, T *__r
 {
     constexpr size_t nt = kFoldDeriveThreads;
     if (!in) {
-        for (size_t k = threadIdx.x; k < n; k += nt) out[k] = ones;
+        for (size_t k = threadIdx.x; k < n; k += nt) fold_store(&out[k], ones);
         return;
     }
     for (size_t k0 = threadIdx.x; k0 < n; k0 += 4 * nt) {    // four loads in flight
@@ -3317,10 +3340,10 @@ __device__ __forceinline__ void fold_copy_elems(const T *__restrict__ in, T *__r
         fold_pin(v1);
         fold_pin(v2);
         fold_pin(v3);
-        out[k0] = v0;
-        if (k1 < n) out[k1] = v1;
-        if (k2 < n) out[k2] = v2;
-        if (k3 < n) out[k3] = v3;
+        fold_store(&out[k0], v0);
+        if (k1 < n) fold_store(&out[k1], v1);
+        if (k2 < n) fold_store(&out[k2], v2);
+        if (k3 < n) fold_store(&out[k3], v3);
     }
 }
 
@@ -3362,7 +3385,8 @@ template <typename T>
 __device__ __forceinline__ void fold_apply(int x, uint32_t wv, int shift, T *row)
 {
     const int w = (int)threadIdx.x / SDNR_WAVE;
-    if (x >= 0 && ((x >> shift) & (kFoldDeriveThreads - 1)) / SDNR_WAVE == w) row[x] = (T)wv;
+    if (x >= 0 && ((x >> shift) & (kFoldDeriveThreads - 1)) / SDNR_WAVE == w)
+        fold_store(&row[x], (T)wv);
 }
 
 // one workgroup per caller row i: the leader's row, then -- for a row that is
