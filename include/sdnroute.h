@@ -716,6 +716,85 @@ int sdnr_fair_rates(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nro
                     double *level, int32_t max_rounds, double *used,
                     int32_t *nrounds /* host */, uint32_t flags);
 
+/* Max-min fair rates of flows split over EVERY least-cost route (ECMP): what
+ * sdnr_fair_rates answers for one path per pair, for the fabric as it is run.
+ * This is the one statement of the definition; ecmp_fair_rates.hip and
+ * engine.ecmp_fair_rates_host follow it step for step.
+ * Flows and fractions.  A flow i is a pair of sdnr_cost_ecmp_link_loads -- row
+ * r of pcost (u32 least-cost rows toward one destination, SDNR_COST_INF: no
+ * route; same pair_off), source vertex srcs[i] -- with sdnr_fair_rates'
+ * multiplicity mult[i] (u64; 0: absent; NULL: all 1; the sum below 2^53) and up
+ * to two extras extra[2*i], extra[2*i+1]: indices in [E, E + nextra) into cap,
+ * -1 for none (extra NULL: none).  Link e = (x -> n) is TIGHT in the row when
+ * pcost[n] != INF and pcost[n] + cost[e] == pcost[x].  The flow's links are the
+ * tight links reachable from its source over tight links, and its fraction
+ * phi_i(e) on each is what sdnr_cost_ecmp_link_loads would put there for unit
+ * weight: route split (sigma[n] / sigma[x] down the DAG, sigma = the number of
+ * least-cost routes to the destination) or, with SDNR_LOADS_SPLIT_HOP, hop
+ * split (evenly over the next hops of every vertex).  The costs are those of
+ * sdnr_graph_costs; with none uploaded every link costs 1, as
+ * sdnr_failure_ecmp_link_loads takes it, so hop-count ECMP is the same call over
+ * distance rows widened to u32.  Every tight link out of a vertex that holds
+ * flow carries a positive fraction under both splits, so "flow i crosses e" is
+ * combinatorial: e is tight and its tail is reachable from the source over
+ * tight links.  cap [E + nextra]: positive finite doubles, the links' in the
+ * uploaded CSR's edge order, then the extras'.
+ * Filling.  rem = cap, used = 0, a_prev = 0, r_{-1} = 0, every flow alive;
+ * round k = 0, 1, ...:
+ *   1. a[e] = sum over the alive flows of mult * phi(e), in f64: the ECMP push
+ *      of the alive multiplicities; for an extra the alive multiplicity itself;
+ *   2. for k > 0: m = max(a_prev[e] - a[e], 0), p = r_{k-1} * m, used[e] += p,
+ *      rem[e] = max(rem[e] - p, 0) -- every operation rounded on its own (no
+ *      FMA);
+ *   3. share[e] = rem[e] / a[e] where a[e] > 0, else +inf;
+ *      r_k = max(min share, r_{k-1}); r_k == +inf ends the rounds;
+ *   4. e is saturated iff share[e] <= r_k + r_k * kFairTie, kFairTie = 2^-30
+ *      (the multiply and the add rounded one by one);
+ *   5. every alive flow that crosses a saturated link or has a saturated extra
+ *      gets rate r_k, round k and bott = the smallest saturated link index it
+ *      crosses, else extra[2*i] if saturated, else extra[2*i+1], and is dead;
+ *      a_prev = a.
+ * One more step 2 after the last round makes used final.  The link with the
+ * smallest share is saturated and some alive flow crosses it, so every round
+ * kills a flow: at most min(flows, E + nextra) rounds.
+ * Why a tolerance.  a[e] is a float sum, so two links whose shares are equal as
+ * fractions differ in their last bits; under ECMP on a symmetric fabric that is
+ * every link of a tier, and sdnr_fair_rates' exact share == r_k would saturate
+ * each in a round of its own.  2^-30 is about 1e-9, the relative tolerance of
+ * the ECMP loads, five orders above their measured summation error: what is not
+ * flagged keeps a margin far above the noise in rem.  The clamp of step 3 makes
+ * the levels non-decreasing by construction.  The consequence: a flow whose
+ * own level lies within 2^-30 (relative) of r_k is frozen at r_k.
+ * Reproducibility.  The adds into a[e] arrive in any order: results equal the
+ * restatement within rounding, and bit for bit where every partial sum is exact
+ * (power-of-two shares and integer multiplicities).
+ *   rate, bott, round, level, used, nrounds, max_rounds: as in sdnr_fair_rates.
+ * A flow with srcs[i] the destination (pcost 0) and no extra: rate +inf, round
+ * -1, bott -1.  A source outside [0, V) or without a route, a multiplicity 0,
+ * and every flow of a rejected row: rate 0.0, round -1, bott -1.  If max_rounds
+ * rounds do not finish the filling, the flows still alive keep rate 0.0, bott
+ * -1 and round -2 and *nrounds is max_rounds.
+ * Device pointers only (flags must hold SDNR_DEVICE_PTRS).  No grid-wide
+ * barrier: a round is two launches on the context's stream (a row kernel in
+ * sdnr_cost_ecmp_link_loads' shape -- sdnr_last_kernel names its form,
+ * "ecmp_fair_rows_kernel<lds>" or "ecmp_fair_rows_kernel<global>" -- and a
+ * kernel over the E + nextra entries); batching behind an 8-byte status word,
+ * sdnr_last_launches, SDNR_TIMING and the multi-device rule as in
+ * sdnr_fair_rates.  nrows == 0 or no pairs: SDNR_OK, *nrounds = 0, nothing else
+ * touched.  pair_off[0] > pair_off[nrows] is SDNR_ERR_INVAL at once.  A row that
+ * is not a least-cost labelling of the graph under the costs in force (a vertex
+ * of finite cost > 0 without a next hop, an ordering pass longer than V, a route
+ * count above the double range: its flows read 0.0 / -1 / -1 and it adds
+ * nothing), offsets of a row outside the pair list, a capacity that is not
+ * positive and finite (taken as +inf) and an extra outside [E, E + nextra)
+ * (ignored) are reported by sdnr_synchronize as SDNR_ERR_INVAL. */
+int sdnr_ecmp_fair_rates(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrows,
+                         const int64_t *pair_off, const int32_t *srcs, const uint64_t *mult,
+                         const int32_t *extra /* [npairs][2] or NULL */, const double *cap,
+                         int32_t nextra, double *rate, int32_t *bott, int32_t *round,
+                         double *level, int32_t max_rounds, double *used,
+                         int32_t *nrounds /* host */, uint32_t flags);
+
 /* Flood ports (TopologyManager._is_edge_port / _do_broadcast, reference
  * sdnmpi/topology.py:150-177): is_edge[i] = 1 iff ports[i] is neither end of
  * any link.  Keys are (dense switch id << 32) | port_no; ends (both ends of

@@ -96,6 +96,14 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "a tree link the graph lacks: that row's flows read 0), pair_off "
                              "outside the pair list, a capacity that is not a positive finite "
                              "number or an extra outside [E, E + nextra): rates invalid");
+        if (h & kErrEcmpFairRates)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: a pcost row is not a "
+                             "least-cost labelling of the uploaded graph under the costs in force "
+                             "(a vertex of finite cost > 0 without a next hop, an ordering pass "
+                             "longer than V, a route count above the double range: that row's "
+                             "flows read 0), pair_off outside the pair list, a capacity that is "
+                             "not a positive finite number or an extra outside [E, E + nextra): "
+                             "rates invalid");
         if (h & kErrCostTables)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_tables: V relaxation sweeps did not reach "
                              "the fixed point (link costs outside what sdnr_graph_costs accepts): "
@@ -1328,6 +1336,48 @@ int sdnr_fair_rates(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nro
     return sdnr_launch_fair_rates(ctx, tree, layout, to_root, nrows, pair_off, lo, hi, verts, mult,
                                   extra, cap, nextra, rate, bott, round, level, max_rounds, used,
                                   nrounds);
+}
+
+int sdnr_ecmp_fair_rates(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrows,
+                         const int64_t *pair_off, const int32_t *srcs, const uint64_t *mult,
+                         const int32_t *extra, const double *cap, int32_t nextra, double *rate,
+                         int32_t *bott, int32_t *round, double *level, int32_t max_rounds,
+                         double *used, int32_t *nrounds, uint32_t flags)
+{
+    CHECK_CTX(ctx);
+    if (!nrounds) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: null nrounds");
+    *nrounds = 0;
+    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_ecmp_fair_rates: no graph uploaded");
+    if (!(flags & SDNR_DEVICE_PTRS))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: device pointers only");
+    if (nrows < 0 || nextra < 0 || max_rounds < 0)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: negative count");
+    if ((int64_t)ctx->E + nextra > 0x7FFFFFFF)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: E + nextra = %lld is no int32",
+                         (long long)ctx->E + nextra);
+    if (nrows == 0) return SDNR_OK;
+    if (!pcost || !pair_off)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: null pointer");
+    SDNR_HIP(hipSetDevice(ctx->device));
+    // the bounds of the pair list: pair_off[0], pair_off[nrows] (two int64)
+    int w[4];
+    int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off), 2, w);
+    if (!rc) rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off + nrows), 2, w + 2);
+    if (rc) return rc;
+    const int64_t lo = (int64_t)(((uint64_t)(uint32_t)w[1] << 32) | (uint32_t)w[0]);
+    const int64_t hi = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
+    if (lo < 0 || hi < lo)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: pair_off not monotone "
+                         "(pair_off[0]=%lld, pair_off[%d]=%lld)", (long long)lo, nrows,
+                         (long long)hi);
+    if (hi == lo) return SDNR_OK;
+    if (!srcs || !rate || !bott || !round || (!level && max_rounds > 0) ||
+        ((!cap || !used) && ctx->E + nextra > 0))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: null pointer");
+    ctx->timed = (flags & SDNR_TIMING) != 0;
+    return sdnr_launch_ecmp_fair_rates(ctx, pcost, nrows, pair_off, lo, hi, srcs, mult, extra, cap,
+                                       nextra, rate, bott, round, level, max_rounds, used, nrounds,
+                                       (flags & SDNR_LOADS_SPLIT_HOP) != 0);
 }
 
 int sdnr_ecmp_link_loads(sdnr_ctx *ctx, const uint16_t *dist, int32_t nrows,

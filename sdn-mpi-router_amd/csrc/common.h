@@ -273,6 +273,22 @@ constexpr int kFairBytesPerV = 24;
 constexpr int kFairLdsMaxV = SDNR_LDS_PER_CU / kFairBytesPerV / 100 * 100;
 static_assert(kFairLdsMaxV == 6800 && kFairLdsMaxV < 0xFFFF, "ancestors in LDS are u16");
 
+constexpr int kErrEcmpFairRates = 2097152; // sdnr_ecmp_fair_rates: a pcost row is no least-cost labelling / bad offsets / a bad capacity or extra
+
+// sdnr_ecmp_fair_rates keeps a row's route counts, flows (the saturated-link
+// search aliases them), costs and depths in LDS (f64 + f64 + u32 + u16: 22
+// bytes per vertex, sdnr_cost_ecmp_link_loads' row state) up to this V -- what
+// the CU's LDS holds beside the kernel's static words (the alive count and the
+// barrier votes, under 512 bytes), rounded down to a hundred: 7,400, 162,800 of
+// 163,840 bytes --, else the counts, flows and
+// depths in global scratch (20 bytes per vertex and workgroup, at most
+// kLoadsScratchBytes in all)
+constexpr int kEcmpFairBytesPerV = 22;
+constexpr int kEcmpFairLdsMaxV = SDNR_LDS_PER_CU / kEcmpFairBytesPerV / 100 * 100;
+static_assert(kEcmpFairLdsMaxV == 7400 && kEcmpFairLdsMaxV < 0xFFFF, "depths in LDS are u16");
+static_assert(kEcmpFairLdsMaxV * kEcmpFairBytesPerV + 16 + 512 <= SDNR_LDS_PER_CU,
+              "the row state, its 16-byte rounding and the static words fit the CU's LDS");
+
 // error plumbing (capi.hip)
 int sdnr_fail(int code, const char *fmt, ...);
 int sdnr_hip_fail(hipError_t e, const char *what);
@@ -391,5 +407,13 @@ int sdnr_launch_fair_rates(sdnr_ctx *ctx, const void *d_tree, int32_t layout, bo
                            const int32_t *d_extra, const double *d_cap, int32_t nextra,
                            double *d_rate, int32_t *d_bott, int32_t *d_round, double *d_level,
                            int32_t max_rounds, double *d_used, int32_t *nrounds);
+// max-min fair rates of flows split over every least-cost route
+// (ecmp_fair_rates.hip); waits for the rounds and writes *nrounds
+int sdnr_launch_ecmp_fair_rates(sdnr_ctx *ctx, const uint32_t *d_pcost, int32_t nrows,
+                                const int64_t *d_pair_off, int64_t pair_lo, int64_t pair_hi,
+                                const int32_t *d_srcs, const uint64_t *d_mult,
+                                const int32_t *d_extra, const double *d_cap, int32_t nextra,
+                                double *d_rate, int32_t *d_bott, int32_t *d_round, double *d_level,
+                                int32_t max_rounds, double *d_used, int32_t *nrounds, bool hop);
 int sdnr_launch_edge_ports(sdnr_ctx *ctx, const uint64_t *d_ends, int32_t nends,
                            const uint64_t *d_ports, int32_t nports, uint8_t *d_is_edge);

@@ -52,7 +52,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_cost_ecmp_link_loads", "sdnr_graph_twin_reps", "sdnr_last_dfs_searched",
     "sdnr_last_dfs_form",
     "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables", "sdnr_whatif_ecmp_link_loads",
-    "sdnr_widest_tables", "sdnr_fair_rates",
+    "sdnr_widest_tables", "sdnr_fair_rates", "sdnr_ecmp_fair_rates",
 )
 
 
@@ -121,6 +121,8 @@ def _bind(L):
         "sdnr_widest_tables": ([vp, vp, vp, vp, i32, vp, vp, vp, u32], c_int),
         "sdnr_fair_rates": ([vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp,
                              ctypes.POINTER(i32), u32], c_int),
+        "sdnr_ecmp_fair_rates": ([vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp,
+                                  ctypes.POINTER(i32), u32], c_int),
         "sdnr_graph_twin_reps": ([vp, vp], c_int),
         "sdnr_last_dfs_searched": ([vp, ctypes.POINTER(i32)], c_int),
         "sdnr_last_dfs_form": ([vp, ctypes.POINTER(i32)], c_int),
@@ -685,6 +687,26 @@ class Context(object):
             self._h, p(tree_ptr), int(layout), int(nrows), p(pair_off_ptr), p(verts_ptr),
             p(mult_ptr), p(extra_ptr), p(cap_ptr), int(nextra), p(rate_ptr), p(bott_ptr),
             p(round_ptr), p(level_ptr), int(max_rounds), p(used_ptr), ctypes.byref(n), flags))
+        return n.value
+
+    def ecmp_fair_rates_device(self, pcost_ptr, nrows, pair_off_ptr, srcs_ptr, mult_ptr,
+                               extra_ptr, cap_ptr, nextra, rate_ptr, bott_ptr, round_ptr,
+                               level_ptr, max_rounds, used_ptr, hop=False, timing=False):
+        """Max-min fair rates of flows split over every least-cost route of
+        [nrows][V] u32 pcost rows under the costs in force (none uploaded:
+        every link costs 1; sdnr_ecmp_fair_rates, device pointers): writes
+        rate (f64), bott and round (i32) per flow, level (f64 [max_rounds])
+        and used (f64 [E + nextra]), and returns the number of rounds.
+        ``mult_ptr`` 0: every flow counts once; ``extra_ptr`` 0: no extra
+        constraints; ``hop``: SDNR_LOADS_SPLIT_HOP.  Waits for the rounds;
+        errors of the rows surface in ``synchronize``."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_SPLIT_HOP if hop else 0)
+        p = lambda a: ctypes.c_void_p(a) if a else None    # noqa: E731
+        n = ctypes.c_int32()
+        _check(self._lib.sdnr_ecmp_fair_rates(
+            self._h, p(pcost_ptr), int(nrows), p(pair_off_ptr), p(srcs_ptr), p(mult_ptr),
+            p(extra_ptr), p(cap_ptr), int(nextra), p(rate_ptr), p(bott_ptr), p(round_ptr),
+            p(level_ptr), int(max_rounds), p(used_ptr), ctypes.byref(n), flags))
         return n.value
 
     def apsp_device(self, dist_ptr, timing=False):

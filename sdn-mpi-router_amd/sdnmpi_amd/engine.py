@@ -49,7 +49,8 @@ __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "whatif_ecmp_link_loads_host", "peak_utilisation", "lfa_tables_host", "LFA_MAX_V", "LFA_BACKUP",
            "LFA_DOWNSTREAM", "LFA_NODE", "widest_tables_host", "check_link_utilisation", "UTIL_MAX",
            "WIDEST_LDS_MAX_V", "WIDEST_LDS_B4_MAX_V", "WIDEST_LDS_B6_MAX_V", "fair_rates_host",
-           "check_fair_flows", "FAIR_LDS_MAX_V", "FAIR_MULT_LIMIT"]
+           "check_fair_flows", "FAIR_LDS_MAX_V", "FAIR_MULT_LIMIT", "ecmp_fair_rates_host",
+           "ECMP_FAIR_LDS_MAX_V", "FAIR_TIE"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -813,6 +814,157 @@ def cost_ecmp_link_loads_host(csr, cost, pcost, rows, srcs, weights=None, split=
     return load
 
 
+ECMP_FAIR_LDS_MAX_V = 7400      # csrc/common.h kEcmpFairLdsMaxV: ECMP fair-rate row state in LDS
+FAIR_TIE = 2.0 ** -30           # ecmp_fair_rates.hip kFairTie: shares within r * FAIR_TIE of r tie
+
+
+def ecmp_fair_rates_host(csr, cost, pcost, rows, srcs, mult, cap, extra=None, split="route"):
+    """numpy restatement of sdnr_ecmp_fair_rates (the CPU tests' engine double
+    and the checker of ecmp_fair_rates.hip): max-min fair rates by progressive
+    filling of flows split over every least-cost route -- flow i enters at
+    switch ``srcs[i]`` of row ``rows[i]`` of ``pcost``, counts ``mult[i]``
+    times (None: once) and is also bound by ``extra[i]`` (two indices in [E, E
+    + nextra) into ``cap`` or -1).  ``cost``: uint32 [E], None: every link
+    costs 1 (``pcost`` rows are hop counts then).  Returns ``(rate float64
+    [n], bott int32 [n], round int32 [n], level float64 [rounds], used float64
+    [E + nextra])``.
+
+    The definition is sdnroute.h's, step for step, each arithmetic step a
+    separate numpy operation.  Every used row is laid out once: its tight
+    links sorted by the pcost of their tail (``cost_ecmp_link_loads_host``'s
+    order; a next hop has a strictly smaller pcost) and its route counts.  A
+    round pushes the alive multiplicities over the groups of equal pcost
+    descending -- group j of every row in one numpy step -- and finds the
+    smallest saturated link below every vertex over them ascending.  The sums
+    into ``a[e]`` run in this order and the device's in any: equal within
+    rounding, bit for bit where every partial sum is exact.  A flow with
+    ``srcs[i]`` the destination and no extra reads +inf / -1 / -1; a source
+    outside [0, V) or without a route and a multiplicity 0 read 0.0 / -1 / -1.
+    A row that is no least-cost labelling raises ValueError."""
+    if split not in SPLITS:
+        raise ValueError("split must be 'route' or 'hop'")
+    V, E = int(csr.V), int(csr.E)
+    rows = np.asarray(rows, np.int64).reshape(-1)
+    srcs = np.asarray(srcs, np.int64).reshape(-1)
+    n = rows.shape[0]
+    mult, cap, extra, nextra = check_fair_flows(E, n, mult, cap, extra)
+    NE = E + nextra
+    c64 = np.ones(E, np.int64) if cost is None else check_link_costs(csr, cost).astype(np.int64)
+    rate = np.zeros(n, np.float64)
+    bott = np.full(n, -1, np.int32)
+    rnd = np.full(n, -1, np.int32)
+    used = np.zeros(NE, np.float64)
+    if n == 0:
+        return rate, bott, rnd, np.zeros(0, np.float64), used
+    pcost = _pcost_u32(pcost)
+    if rows.min() < 0 or rows.max() >= pcost.shape[0]:
+        raise ValueError("ecmp_fair_rates_host: a pair names a row outside the table")
+    urows, rix = np.unique(rows, return_inverse=True)
+    R = urows.shape[0]
+    RV = R * V
+    pc = pcost[urows].astype(np.int64)
+    fin = pc != COST_INF
+    rp = np.asarray(csr.row_ptr, np.int64)
+    esrc = np.repeat(np.arange(V, dtype=np.int64), np.diff(rp))
+    edst = np.asarray(csr.col, np.int64)
+    # the tight links of every used row, with the rank of their tail's pcost in the row
+    le, lx, ln, lj = [], [], [], []
+    for k in range(R):
+        p = pc[k]
+        dag = np.nonzero(fin[k][esrc] & (p[esrc] > 0) & fin[k][edst] & (p[edst] + c64 == p[esrc]))[0]
+        dag = dag[np.argsort(p[esrc[dag]], kind="stable")]
+        _, j = np.unique(p[esrc[dag]], return_inverse=True)
+        le.append(dag)
+        lx.append(esrc[dag] + k * V)
+        ln.append(edst[dag] + k * V)
+        lj.append(j.reshape(-1))
+    le, lx, ln, lj = (np.concatenate(a) if a else np.zeros(0, np.int64) for a in (le, lx, ln, lj))
+    order = np.argsort(lj, kind="stable")
+    le, lx, ln, lj = le[order], lx[order], ln[order], lj[order]
+    ends = np.cumsum(np.bincount(lj)) if lj.size else np.zeros(0, np.int64)
+    groups = list(zip(np.append(0, ends[:-1]).tolist(), ends.tolist())) if lj.size else []
+    sigma = np.zeros(RV, np.float64)
+    if split == "hop":
+        sigma += np.bincount(lx, minlength=RV)
+        q = None
+    else:
+        sigma[(pc == 0).ravel()] = 1.0
+        for a, b in groups:
+            sigma += np.bincount(lx[a:b], sigma[ln[a:b]], minlength=RV)
+    if ((fin & (pc > 0)).ravel() & ~(sigma > 0)).any() or not np.isfinite(sigma).all():
+        raise ValueError("ecmp_fair_rates_host: a row is not a least-cost labelling of the "
+                         "graph under these costs")
+    if split != "hop":
+        q = sigma[ln] / sigma[lx]
+
+    inside = (srcs >= 0) & (srcs < V)
+    at = rix.reshape(-1) * V + np.where(inside, srcs, 0)
+    pcs = pc.ravel()[at]
+    x0, x1 = extra[:, 0], extra[:, 1]
+    there = inside & (mult > 0) & (pcs != COST_INF)
+    bare = there & (pcs == 0) & (x0 < 0) & (x1 < 0)
+    rate[bare] = np.inf
+    alive = there & ~bare
+    fmult = mult.astype(np.float64)
+
+    none = np.int64(1) << 62
+    rem = cap.copy()
+    a_prev = np.zeros(NE, np.float64)
+    level = []
+    r_prev = np.float64(0.0)
+    inf = np.float64(np.inf)
+    for k in range(n + 2):
+        # 1. the ECMP push of the alive multiplicities
+        al = np.nonzero(alive)[0]
+        flow = np.bincount(at[al], fmult[al], minlength=RV).astype(np.float64)
+        cnt = np.zeros(NE, np.float64)
+        for a, b in groups[::-1]:
+            x = lx[a:b]
+            g = flow[x] / sigma[x] if q is None else flow[x] * q[a:b]
+            cnt += np.bincount(le[a:b], g, minlength=NE)
+            flow += np.bincount(ln[a:b], g, minlength=RV)
+        a0 = al[x0[al] >= 0]
+        np.add.at(cnt, x0[a0], fmult[a0])
+        a1 = al[(x1[al] >= 0) & (x1[al] != x0[al])]
+        np.add.at(cnt, x1[a1], fmult[a1])
+        # 2. what the flows frozen last round carry
+        if k > 0:
+            m = np.maximum(a_prev - cnt, 0.0)
+            p = r_prev * m
+            used = used + p
+            rem = np.maximum(rem - p, 0.0)
+        # 3. the next level, never below the last
+        share = np.full(NE, inf)
+        np.divide(rem, cnt, out=share, where=cnt > 0)
+        r = share.min() if NE else inf
+        r = max(r, r_prev)
+        if r == inf:
+            break
+        level.append(r)
+        # 4. saturated: within the tie tolerance of the level
+        t = r * np.float64(FAIR_TIE)
+        sat = share <= r + t
+        # 5. the smallest saturated link below every vertex, else a saturated extra
+        B = np.full(RV, none, np.int64)
+        for a, b in groups:
+            e = le[a:b]
+            np.minimum.at(B, lx[a:b], np.minimum(np.where(sat[e], e, none), B[ln[a:b]]))
+        bb = B[at[al]]
+        e0, e1 = x0[al], x1[al]
+        s0 = (e0 >= 0) & sat[np.where(e0 >= 0, e0, 0)] if NE else e0 >= 0
+        s1 = (e1 >= 0) & sat[np.where(e1 >= 0, e1, 0)] if NE else e1 >= 0
+        bb = np.where(bb != none, bb, np.where(s0, e0, np.where(s1, e1, -1)))
+        hit = al[bb >= 0]
+        rate[hit] = r
+        rnd[hit] = k
+        bott[hit] = bb[bb >= 0]
+        alive[hit] = False
+        a_prev, r_prev = cnt, r
+    else:
+        raise AssertionError("ecmp_fair_rates_host: a round froze no flow")
+    return rate, bott, rnd, np.asarray(level, np.float64), used
+
+
 FAILURE_LDS_MAX_V = 7100        # csrc/common.h kFailureLdsMaxV: what-if row state in LDS
 
 
@@ -1468,6 +1620,87 @@ class RouteEngine(object):
             rnd.data_ptr(), level.data_ptr() if max_rounds else 0, max_rounds,
             used.data_ptr() if NE else 0, to_root=to_root, timing=timing)
         self.ctx.synchronize()              # raises if a row was not a tree
+        out = []
+        for a in (rate, bott, rnd):
+            a = a.cpu().numpy()
+            if not isinstance(order, slice):
+                back = np.empty_like(a)
+                back[order] = a
+                a = back
+            out.append(a)
+        return out[0], out[1], out[2], level.cpu().numpy()[:rounds], used.cpu().numpy()
+
+    def ecmp_fair_rates(self, export, cost, pcost, rows, srcs, mult=None, cap=None, extra=None,
+                        split="route", timing=False):
+        """Max-min fair rates of flows split over every least-cost route
+        (ecmp_fair_rates.hip, sdnr_ecmp_fair_rates): ``(rate float64 [n], bott
+        int32 [n], round int32 [n], level float64 [rounds], used float64 [E +
+        nextra])`` in the flows' order, what ``ecmp_fair_rates_host`` returns
+        within rounding (bit for bit where every partial sum is exact).
+
+        ``cost``: uint32 [E], uploaded as ``cost_tables`` uploads it; None
+        clears the context's costs: every link costs 1 and ``pcost`` holds hop
+        counts.  ``pcost``, ``rows``, ``srcs``, ``split`` as in
+        ``cost_ecmp_link_loads``; ``mult``, ``cap``, ``extra`` as in
+        ``fair_rates``.  The flows are sorted by row here and every row stays
+        on the device across the rounds."""
+        if split not in SPLITS:
+            raise ValueError("split must be 'route' or 'hop'")
+        if cost is None:
+            self.load(export)
+            if self._costs is not None:
+                self._costs = None
+                self.ctx.set_link_costs(None)
+        else:
+            self.set_link_costs(export, cost)
+        t = self._torch
+        V, E = int(export.csr.V), int(export.csr.E)
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        n = rows.shape[0]
+        if cap is None:
+            cap = np.ones(E, np.float64)
+        mult_in = mult
+        mult, cap, extra_all, nextra = check_fair_flows(E, n, mult, cap, extra)
+        NE = E + nextra
+        if isinstance(pcost, np.ndarray):
+            pcost = t.from_numpy(np.ascontiguousarray(_pcost_u32(pcost)).view(np.int32)).to(
+                self.dev)
+        nrows = int(pcost.shape[0])
+        if n == 0 or nrows == 0:
+            if n:
+                raise ValueError("ecmp_fair_rates: a pair names a row outside the table")
+            return (np.zeros(0, np.float64), np.zeros(0, np.int32), np.zeros(0, np.int32),
+                    np.zeros(0, np.float64), np.zeros(NE, np.float64))
+        if rows.min() < 0 or rows.max() >= nrows:
+            raise ValueError("ecmp_fair_rates: a pair names a row outside the table")
+        if pcost.element_size() != 4:
+            raise ValueError("ecmp_fair_rates: pcost rows are 32-bit")
+        order, off = _pairs_by_row(rows, nrows)
+        x = np.asarray(srcs, np.int64).reshape(-1)[order]
+        x = np.where((x < 0) | (x >= V), -1, x).astype(np.int32)
+        pcost = pcost.contiguous()
+        d_off = t.from_numpy(off).to(self.dev)
+        d_x = t.from_numpy(x).to(self.dev)
+        d_m = d_e = None
+        if mult_in is not None:
+            d_m = t.from_numpy(np.ascontiguousarray(mult[order]).view(np.int64)).to(self.dev)
+        if extra is not None:
+            d_e = t.from_numpy(np.ascontiguousarray(extra_all[order].astype(np.int32))).to(self.dev)
+        d_cap = t.from_numpy(cap).to(self.dev)
+        max_rounds = min(n, NE)
+        rate = t.empty(n, dtype=t.float64, device=self.dev)
+        bott = t.empty(n, dtype=t.int32, device=self.dev)
+        rnd = t.empty(n, dtype=t.int32, device=self.dev)
+        level = t.empty(max_rounds, dtype=t.float64, device=self.dev)
+        used = t.zeros(NE, dtype=t.float64, device=self.dev)
+        self._ready()
+        rounds = self.ctx.ecmp_fair_rates_device(
+            pcost.data_ptr(), nrows, d_off.data_ptr(), d_x.data_ptr(),
+            d_m.data_ptr() if d_m is not None else 0, d_e.data_ptr() if d_e is not None else 0,
+            d_cap.data_ptr() if NE else 0, nextra, rate.data_ptr(), bott.data_ptr(),
+            rnd.data_ptr(), level.data_ptr() if max_rounds else 0, max_rounds,
+            used.data_ptr() if NE else 0, hop=split == "hop", timing=timing)
+        self.ctx.synchronize()              # raises if a row was no least-cost labelling
         out = []
         for a in (rate, bott, rnd):
             a = a.cpu().numpy()

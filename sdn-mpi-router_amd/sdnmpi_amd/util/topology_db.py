@@ -2271,6 +2271,7 @@ class TopologyDB(object):
 
     # -- max-min fair rates ------------------------------------------------
     FAIR_ROUTES = ("default", "shortest", "least_cost", "least_loaded")
+    FAIR_ECMP_ROUTES = ("ecmp", "least_cost_ecmp")
 
     def _fair_rows(self, ex, route, sv, dv):
         """The single-path tables of ``route`` for switch pairs sv -> dv, all
@@ -2281,7 +2282,8 @@ class TopologyDB(object):
         every row, so a call is not chunked: rows beyond the table budget are
         a ValueError."""
         if route not in self.FAIR_ROUTES:
-            raise ValueError("route must be one of %s" % ", ".join(map(repr, self.FAIR_ROUTES)))
+            raise ValueError("route must be one of %s" % ", ".join(
+                map(repr, self.FAIR_ROUTES + self.FAIR_ECMP_ROUTES)))
         V = int(ex.csr.V)
         budget = int(DEFAULT_TABLE_BUDGET if self._budget is None else self._budget)
         c = self._cache
@@ -2323,6 +2325,44 @@ class TopologyDB(object):
         nh = nh.astype(np.int32) if isinstance(nh, np.ndarray) else nh.to(dtype=_torch().int32)
         return nh, INT32, inv.reshape(-1), other, True, reach
 
+    def _fair_ecmp_rows(self, ex, route, sv, dv):
+        """The multipath tables of ``route`` for switch pairs sv -> dv, all of
+        their rows resident at once: (cost, pcost, rows, reach) as
+        ``engine.ecmp_fair_rates`` takes them.  ``"ecmp"``: the cached
+        distance rows of the destinations widened to 32 bits, no costs (every
+        link costs 1); ``"least_cost_ecmp"``: the memoised least-cost rows
+        under the link costs in force.  More rows than the table budget holds
+        are a ValueError, as in :meth:`_fair_rows`."""
+        V = int(ex.csr.V)
+        budget = int(DEFAULT_TABLE_BUDGET if self._budget is None else self._budget)
+        want = sorted(set(dv.tolist()))
+        if route == "ecmp":
+            store = self._cache.sp
+            room = max(1, store.cap() - 1) if store.row_bytes else 1 << 62
+            room = min(room, max(1, budget // max(1, 4 * V)))   # the rows are widened to 32 bits
+        else:
+            room = self._cost_cap(ex)
+        if len(want) > room:
+            raise ValueError("fair rates keep every table row of a call resident across the "
+                             "rounds: %d %s rows exceed the table budget of %d bytes (%d rows)"
+                             % (len(want), route, budget, room))
+        if route == "ecmp":
+            batch = self._host_vertices(ex) if self._batch else ()
+            tabs = self._cache.sp_rows(self.engine, want, batch)
+            slots = np.asarray([store.row[v] for v in dv.tolist()], np.int64)
+            # the distance plane holds -1 (u16 0xFFFF as int16) where unreached
+            reach = _gather(tabs[0], slots, sv) != -1
+            urows, inv = np.unique(slots, return_inverse=True)
+            d = _u16(_take(tabs[0], urows))                      # unreached: -1, COST_INF as u32
+            d = d.astype(np.int32) if isinstance(d, np.ndarray) else d.to(dtype=_torch().int32)
+            return None, d, inv.reshape(-1), reach
+        m = self._cost_rows(ex, want)
+        slots = np.asarray([m["slot"][v] for v in dv.tolist()], np.int64)
+        pc = m["tabs"][0]
+        # pcost is held as int32: COST_INF reads -1
+        reach = _gather(pc, slots, sv) != -1
+        return self._cost_vector(ex), pc, slots, reach
+
     def _fair_capacity(self, ex, capacity):
         """float64 [E] link capacities: None 1.0 each, a positive number for
         every link, or a mapping as :meth:`_capacity_vector` takes it."""
@@ -2336,11 +2376,24 @@ class TopologyDB(object):
             return np.full(E, float(capacity), np.float64)
         return self._capacity_vector(ex, capacity)
 
-    def _fair(self, ex, pairs, w, sv, dv, ports, capacity, host_capacity, route):
+    def _fair(self, ex, pairs, w, sv, dv, ports, capacity, host_capacity, route, split="route"):
         """FairRates of pairs already resolved: dense switches sv -> dv (-1:
         unknown host), multiplicities w, and per pair ``ports`` = (source
         switch port, destination switch port, source MAC, destination MAC) for
         the host-port constraints (None: not modelled)."""
+        if split not in ("route", "hop"):
+            raise ValueError("split must be 'route' or 'hop'")
+        if route not in self.FAIR_ROUTES + self.FAIR_ECMP_ROUTES:
+            raise ValueError("route must be one of %s" % ", ".join(
+                map(repr, self.FAIR_ROUTES + self.FAIR_ECMP_ROUTES)))
+        if route in self.FAIR_ECMP_ROUTES and not hasattr(self.engine, "ecmp_fair_rates"):
+            # (a missing kernel is an error, never a fall-back to one path per pair)
+            raise ValueError("route=%r needs an engine with ecmp_fair_rates (the multipath "
+                             "filling); this one offers only the single-path routes %s"
+                             % (route, ", ".join(map(repr, self.FAIR_ROUTES))))
+        if split != "route" and route not in self.FAIR_ECMP_ROUTES:
+            raise ValueError("split=%r needs a multipath route (%s): %r puts a pair on one path"
+                             % (split, ", ".join(map(repr, self.FAIR_ECMP_ROUTES)), route))
         n = sv.shape[0]
         E, V = int(ex.csr.E), int(ex.csr.V)
         if sum(int(x) for x in w.tolist()) >= FAIR_MULT_LIMIT:
@@ -2387,12 +2440,17 @@ class TopologyDB(object):
         used = np.zeros(cap.shape[0], np.float64)
         if fkey.shape[0]:
             fs, fd = fkey[:, 0], fkey[:, 1]
-            tree, layout, rows, verts, to_root, reach = self._fair_rows(ex, route, fs, fd)
-            # (next-hop rows cannot tell an unreached vertex from the root)
-            verts = np.where(reach, verts, -1)
             extra = fkey[:, 2:4] if host_capacity is not None else None
-            r, b, k, levels, used = self.engine.fair_rates(ex, tree, layout, rows, verts, fw, cap,
-                                                           extra, to_root=to_root)
+            if route in self.FAIR_ECMP_ROUTES:
+                cost, pcost, rows, reach = self._fair_ecmp_rows(ex, route, fs, fd)
+                r, b, k, levels, used = self.engine.ecmp_fair_rates(ex, cost, pcost, rows, fs, fw,
+                                                                    cap, extra, split)
+            else:
+                tree, layout, rows, verts, to_root, reach = self._fair_rows(ex, route, fs, fd)
+                # (next-hop rows cannot tell an unreached vertex from the root)
+                verts = np.where(reach, verts, -1)
+                r, b, k, levels, used = self.engine.fair_rates(ex, tree, layout, rows, verts, fw,
+                                                               cap, extra, to_root=to_root)
             rate[ok], rnd[ok], bott[ok], routed[ok] = r[finv], k[finv], b[finv], reach[finv]
         link = self._edge_links(ex)
 
@@ -2404,7 +2462,8 @@ class TopologyDB(object):
         return FairRates(pairs, w, rate, routed, rnd, bottleneck, levels, link_rate, cap, used,
                          names)
 
-    def fair_rates(self, pairs, weights=None, capacity=None, host_capacity=None, route="default"):
+    def fair_rates(self, pairs, weights=None, capacity=None, host_capacity=None, route="default",
+                   split="route"):
         """What every (src_mac, dst_mac) pair of ``pairs`` gets when all of
         them send at once and share the links max-min fairly, as TCP or RoCE
         (DCQCN) flows approximately do: the rate of each pair, the link that
@@ -2414,7 +2473,14 @@ class TopologyDB(object):
         ``route``: which single path a pair takes -- ``"default"``
         (:meth:`find_route`), ``"shortest"`` (``find_route(multiple=True)[0]``),
         ``"least_cost"`` (:meth:`find_route_least_cost`) or ``"least_loaded"``
-        (:meth:`find_route_least_loaded`).  ``weights``: multiplicities --
+        (:meth:`find_route_least_loaded`) --, or the set it is spread over:
+        ``"ecmp"`` (every route of ``find_route(multiple=True)``, hop-count
+        ECMP) or ``"least_cost_ecmp"`` (every route of
+        ``find_route_least_cost(multiple=True)``).  ``split``: how a multipath
+        route divides a pair, as in :meth:`ecmp_link_loads` -- ``"route"``
+        (evenly over its routes) or ``"hop"`` (evenly over the next hops of
+        every switch); anything but ``"route"`` with a single-path ``route``
+        is a ValueError.  ``weights``: multiplicities --
         pair i stands for ``weights[i]`` identical parallel flows, each of
         which gets ``rate[i]`` (non-negative ints, None: 1; 0: absent; the sum
         must stay below 2**53, else ValueError).  ``capacity``: ``{(src_dpid,
@@ -2430,8 +2496,12 @@ class TopologyDB(object):
         is unique; the GPU runs the rounds (fair_rates.hip), bit for bit equal
         to ``engine.fair_rates_host``.  Every table row the pairs need stays
         resident across the rounds: more rows than the table budget holds are
-        a ValueError, not chunked.  Flows split over several routes (ECMP
-        fractions) are out of scope: every pair is on one path."""
+        a ValueError, not chunked.  Under the multipath routes a pair puts its
+        ECMP fraction of its rate on every link of its route set
+        (ecmp_fair_rates.hip; ``engine.ecmp_fair_rates_host`` within
+        rounding); the link counts are float sums there, so links whose shares
+        lie within 2**-30 (relative) of a level saturate with it, and a pair
+        within that of a level is frozen at it."""
         ex = self.graph()
         pairs = list(pairs)
         n = len(pairs)
@@ -2449,20 +2519,21 @@ class TopologyDB(object):
             sport[i] = self._last_hop(ea[0], ea[1], a)[1]
             dport[i] = self._last_hop(eb[0], eb[1], b)[1]
         ports = (sport, dport, [a for a, _ in pairs], [b for _, b in pairs])
-        return self._fair(ex, pairs, w, sv, dv, ports, capacity, host_capacity, route)
+        return self._fair(ex, pairs, w, sv, dv, ports, capacity, host_capacity, route, split)
 
-    def all_pairs_fair_rates(self, capacity=None, route="default"):
+    def all_pairs_fair_rates(self, capacity=None, route="default", split="route"):
         """:meth:`fair_rates` of every ordered pair of distinct hosts at once
         (all-to-all traffic), in the switch-pair form: ``pairs`` of the result
         are ``(src_dpid, dst_dpid)`` over the host-bearing switches and
         ``weights`` their host pairs, hosts(s) * (hosts(d) - [s == d]); host
-        ports are not modelled.  When a host MAC names a switch the MAC-pair
+        ports are not modelled.  ``route`` and ``split`` as in
+        :meth:`fair_rates`.  When a host MAC names a switch the MAC-pair
         form is taken (``pairs`` are MAC pairs then), as in
         :meth:`all_pairs_link_loads`."""
         if any(self._mac_to_int(m) in self.switches for m in self.hosts):
             macs = list(self.hosts)
             return self.fair_rates([(a, b) for a in macs for b in macs if a != b], None, capacity,
-                                   None, route)
+                                   None, route, split)
         ex = self.graph()
         hv = np.asarray(self._host_vertices(ex), np.int64)
         hc = np.asarray(ex.host_count, np.int64)
@@ -2471,10 +2542,10 @@ class TopologyDB(object):
         w = (hc[sv] * (hc[dv] - (sv == dv))).astype(np.uint64)
         dp = ex.csr.dpids
         pairs = list(zip(dp[sv].tolist(), dp[dv].tolist()))
-        return self._fair(ex, pairs, w, sv, dv, None, capacity, None, route)
+        return self._fair(ex, pairs, w, sv, dv, None, capacity, None, route, split)
 
     def mpi_fair_rates(self, rank_to_mac, traffic=None, capacity=None, host_capacity=None,
-                       route="default"):
+                       route="default", split="route"):
         """:meth:`fair_rates` of an MPI job's exchange: the keys of ``traffic``
         = {(src_rank, dst_rank): bytes} give the pairs, one flow each (None:
         every ordered rank pair i != j, one byte each).  The result also has
@@ -2482,9 +2553,10 @@ class TopologyDB(object):
         pair without a route, 0.0 for no bytes), and ``step_time()``, the
         largest: the exchange's duration if the rates held throughout -- flows
         that finish early would leave their share to the rest, so the real
-        exchange is no slower than that."""
+        exchange is no slower than that.  ``route`` and ``split`` as in
+        :meth:`fair_rates`."""
         pairs, nbytes = self._rank_pairs(rank_to_mac, traffic)
-        res = self.fair_rates(pairs, None, capacity, host_capacity, route)
+        res = self.fair_rates(pairs, None, capacity, host_capacity, route, split)
         b = np.ones(len(pairs), np.float64) if nbytes is None else \
             np.asarray([float(x) for x in nbytes], np.float64).reshape(-1)
         if (b < 0).any():
