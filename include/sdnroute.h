@@ -824,6 +824,13 @@ int sdnr_last_dfs_searched(sdnr_ctx *ctx, int32_t *n);
  * (does not wait; both forms compute the same tables). */
 int sdnr_last_dfs_form(const sdnr_ctx *ctx, int32_t *form);
 
+/* Whether the search kernel of the last sdnr_dfs_tables* call ran on the
+ * graph's twin-class quotient (1) or on the graph itself (0): the quotient is
+ * taken where the graph has twins and its quotient at most half the links
+ * (SDNROUTE_DFS_QUOTIENT=0|1 forces it; does not wait; the tables are the
+ * same either way). */
+int sdnr_last_dfs_quotient(const sdnr_ctx *ctx, int32_t *on);
+
 /* Bellman-Ford sweeps of the last sdnr_apsp call (the most any 8-row block
  * ran, summed over its relaxation launches; 0 with SDNROUTE_APSP_RELAX=0). */
 int sdnr_last_sweeps(const sdnr_ctx *ctx, int32_t *sweeps);

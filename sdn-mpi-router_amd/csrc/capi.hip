@@ -191,6 +191,21 @@ static void free_graph(sdnr_ctx *c)
     c->adjb = nullptr;
     c->adjp = nullptr;
     c->radjx = nullptr;
+    if (c->q_radj16 && c->q_radj_owned) (void)hipFree(c->q_radj16);
+    {
+        void **qb[] = {reinterpret_cast<void **>(&c->q_adj16), reinterpret_cast<void **>(&c->q_deg32),
+                       reinterpret_cast<void **>(&c->q_radjw), reinterpret_cast<void **>(&c->q_radjc),
+                       reinterpret_cast<void **>(&c->q_cid), reinterpret_cast<void **>(&c->q_info),
+                       reinterpret_cast<void **>(&c->q_loff), reinterpret_cast<void **>(&c->q_slot),
+                       reinterpret_cast<void **>(&c->q_tab)};
+        for (void **b : qb) {
+            if (*b) (void)hipFree(*b);
+            *b = nullptr;
+        }
+    }
+    c->q_radj16 = nullptr;
+    c->q_radj_owned = false;
+    c->q_V = c->q_E = 0;
     if (c->adj16) (void)hipFree(c->adj16);
     if (c->deg32) (void)hipFree(c->deg32);
     if (c->radjw) (void)hipFree(c->radjw);
@@ -530,7 +545,7 @@ static int upload_dict(sdnr_ctx *ctx, int32_t V, int32_t W, const int32_t *row_p
 // leaving those out is the whole of "neither is in the other's row".  Rows
 // are hashed, vertices sorted by hash, and equal hashes compared exactly.
 static int upload_twins(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *row_ptr,
-                        const int32_t *col)
+                        const int32_t *col, std::vector<int32_t> *rep_out)
 {
     if (V == 0) return SDNR_OK;
     std::vector<int32_t> in_ptr((size_t)V + 1, 0), in_col((size_t)E);
@@ -587,6 +602,7 @@ static int upload_twins(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *row_
     if (rc) return rc;
     SDNR_HIP(hipStreamSynchronize(ctx->stream));  // before rep goes away
     ctx->has_twins = any;
+    rep_out->swap(rep);
     return SDNR_OK;
 }
 
@@ -642,7 +658,8 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
         free_graph(ctx);
         return rc;
     }
-    if ((rc = upload_twins(ctx, V, E, row_ptr, col))) {
+    std::vector<int32_t> twin_rep;               // host copy, for the quotient below
+    if ((rc = upload_twins(ctx, V, E, row_ptr, col, &twin_rep))) {
         free_graph(ctx);
         return rc;
     }
@@ -705,9 +722,19 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
     // in-neighbour rows (same layout) and packed out-degrees feed the
     // counted-pop kernel
     int32_t max_indeg = 0x7FFFFFFF;             // known only with the u16 rows
-    if (V < 65535 && maxdeg <= SDNR_WAVE) {
+    // the rows of one graph: the uploaded one, and its twin-class quotient
+    // (paired: -1 as the in-degrees allow, else 0 / 1 as the caller says)
+    struct U16Rows {
+        uint16_t *adj16 = nullptr, *radj16 = nullptr, *radjw = nullptr, *radjc = nullptr;
+        uint32_t *deg32 = nullptr;
+        bool radj_owned = false, radj_pair = false;
+    };
+    auto upload_u16_rows = [ctx](U16Rows &o, int32_t V, const int32_t *row_ptr, const int32_t *col,
+                                 std::vector<uint16_t> &a16, std::vector<uint16_t> &r16, bool &sym,
+                                 int32_t &maxin, int paired) -> hipError_t {
         const size_t rows = ((size_t)V + 1) * SDNR_WAVE;
-        std::vector<uint16_t> a16(rows, (uint16_t)V), r16(rows, (uint16_t)V);
+        a16.assign(rows, (uint16_t)V);
+        r16.assign(rows, (uint16_t)V);
         std::vector<int32_t> indeg((size_t)V + 1, 0);
         std::vector<uint32_t> d32(((size_t)V + 2) & ~(size_t)1, 0u);   // even: read in pairs
         for (int32_t u = 0; u < V; ++u) {
@@ -718,10 +745,9 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
                 indeg[col[e]]++;
             }
         }
-        int32_t maxin = 0;
+        maxin = 0;
         for (int32_t v = 0; v < V; ++v) maxin = indeg[v] > maxin ? indeg[v] : maxin;
-        max_indeg = maxin;
-        bool sym = true;
+        sym = true;
         if (maxin <= SDNR_WAVE) {
             std::vector<int32_t> fill((size_t)V, 0);
             for (int32_t u = 0; u < V; ++u)       // ascending u: rows come out sorted
@@ -731,21 +757,21 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
                 }
             sym = a16 == r16;
         }
-        hipError_t he = hipMalloc(reinterpret_cast<void **>(&ctx->adj16), rows * 2);
+        hipError_t he = hipMalloc(reinterpret_cast<void **>(&o.adj16), rows * 2);
         if (he == hipSuccess)
-            he = hipMemcpyAsync(ctx->adj16, a16.data(), rows * 2, hipMemcpyHostToDevice, ctx->stream);
+            he = hipMemcpyAsync(o.adj16, a16.data(), rows * 2, hipMemcpyHostToDevice, ctx->stream);
         if (he == hipSuccess && maxin <= SDNR_WAVE) {
-            he = hipMalloc(reinterpret_cast<void **>(&ctx->deg32), d32.size() * 4);
+            he = hipMalloc(reinterpret_cast<void **>(&o.deg32), d32.size() * 4);
             if (he == hipSuccess)
-                he = hipMemcpyAsync(ctx->deg32, d32.data(), d32.size() * 4, hipMemcpyHostToDevice,
+                he = hipMemcpyAsync(o.deg32, d32.data(), d32.size() * 4, hipMemcpyHostToDevice,
                                     ctx->stream);
             if (he == hipSuccess && sym) {
-                ctx->radj16 = ctx->adj16;
+                o.radj16 = o.adj16;
             } else if (he == hipSuccess) {
-                he = hipMalloc(reinterpret_cast<void **>(&ctx->radj16), rows * 2);
-                ctx->radj_owned = he == hipSuccess;
+                he = hipMalloc(reinterpret_cast<void **>(&o.radj16), rows * 2);
+                o.radj_owned = he == hipSuccess;
                 if (he == hipSuccess)
-                    he = hipMemcpyAsync(ctx->radj16, r16.data(), rows * 2, hipMemcpyHostToDevice,
+                    he = hipMemcpyAsync(o.radj16, r16.data(), rows * 2, hipMemcpyHostToDevice,
                                         ctx->stream);
             }
         }
@@ -764,17 +790,17 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
             // dummies stay per lane), so a worker pairs two children per load
             const bool pair = maxin <= SDNR_WAVE / 2;
             const char *pe = sdnr_tune_env("SDNROUTE_DFS_PAIR");          // 0: off (A/B)
-            ctx->radj_pair = pair && !(pe && !strcmp(pe, "0"));
+            o.radj_pair = pair && (paired < 0 ? !(pe && !strcmp(pe, "0")) : paired == 1);
             auto at = [&](size_t i) {
-                return ctx->radj_pair ? (i & ~(size_t)(SDNR_WAVE / 2)) : i;   // lane l -> l & 31
+                return o.radj_pair ? (i & ~(size_t)(SDNR_WAVE / 2)) : i;   // lane l -> l & 31
             };
             for (size_t i = 0; i < w16.size(); ++i) {
                 const int x = src16[at(i)];
                 w16[i] = (uint16_t)(x == V ? (int)(dummy + i % SDNR_WAVE) : (x ^ ((x >> 3) & 31)));
             }
-            he = hipMalloc(reinterpret_cast<void **>(&ctx->radjw), w16.size() * 2);
+            he = hipMalloc(reinterpret_cast<void **>(&o.radjw), w16.size() * 2);
             if (he == hipSuccess)
-                he = hipMemcpyAsync(ctx->radjw, w16.data(), w16.size() * 2, hipMemcpyHostToDevice,
+                he = hipMemcpyAsync(o.radjw, w16.data(), w16.size() * 2, hipMemcpyHostToDevice,
                                     ctx->stream);
             if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
             // the same for the compact-LDS kernel (u16 counts in pairs):
@@ -787,13 +813,30 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
                     w16[i] = (uint16_t)(x == V ? (int)(2 * (dummyc + i % SDNR_WAVE))
                                                : ((h ^ ((h >> 3) & 31)) << 1) | (x & 1));
                 }
-                he = hipMalloc(reinterpret_cast<void **>(&ctx->radjc), w16.size() * 2);
+                he = hipMalloc(reinterpret_cast<void **>(&o.radjc), w16.size() * 2);
                 if (he == hipSuccess)
-                    he = hipMemcpyAsync(ctx->radjc, w16.data(), w16.size() * 2,
+                    he = hipMemcpyAsync(o.radjc, w16.data(), w16.size() * 2,
                                         hipMemcpyHostToDevice, ctx->stream);
                 if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
             }
         }
+        if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);   // before the host rows go
+        return he;
+    };
+    if (V < 65535 && maxdeg <= SDNR_WAVE) {
+        std::vector<uint16_t> a16, r16;
+        bool sym = true;
+        int32_t maxin = 0;
+        U16Rows o;
+        hipError_t he = upload_u16_rows(o, V, row_ptr, col, a16, r16, sym, maxin, -1);
+        ctx->adj16 = o.adj16;
+        ctx->radj16 = o.radj16;
+        ctx->deg32 = o.deg32;
+        ctx->radjw = o.radjw;
+        ctx->radjc = o.radjc;
+        ctx->radj_owned = o.radj_owned;
+        ctx->radj_pair = o.radj_pair;
+        max_indeg = maxin;
 #ifdef SDNR_DIAG_VARIANTS
         // diagnostic build only (tools/diag/): the losing DFS variants' rows
         // the out-rows as arithmetic runs for the LDS-row DFS (dfs_runs.hip)
@@ -857,6 +900,91 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
         if (he != hipSuccess) {
             free_graph(ctx);
             return sdnr_hip_fail(he, "graph_upload(adj16)");
+        }
+        // the twin-class quotient for dfs_async_kernel (common.h, DESIGN.md
+        // 4.1e): classes numbered by ascending largest member; the out-row of
+        // a class is the sorted set of its members' neighbours' classes.  Its
+        // u16 rows come from the code above, paired exactly when the graph's
+        // are (its in-degrees are no larger), so every rule that looks at the
+        // graph's row form picks the same kernel form for the quotient
+        if (ctx->has_twins && ctx->radj16) {
+            std::vector<int32_t> cmax_of((size_t)V), id_of((size_t)V, -1);
+            for (int32_t v = 0; v < V; ++v) cmax_of[twin_rep[v]] = v;   // ascending: the largest
+            int32_t Vq = 0;
+            for (int32_t v = 0; v < V; ++v)
+                if (cmax_of[twin_rep[v]] == v) id_of[twin_rep[v]] = Vq++;
+            std::vector<uint32_t> cidrk((size_t)V + kPad, 0u), info((size_t)Vq + 1, 0u),
+                csize((size_t)Vq, 0u);
+            for (int32_t v = 0; v < V; ++v) {
+                const uint32_t c = (uint32_t)id_of[twin_rep[v]];
+                cidrk[v] = c | (csize[c]++ << 16);
+                info[c] = (uint32_t)v;                                  // ascending: the largest
+            }
+            for (int32_t c = 0; c < Vq; ++c) info[c] |= csize[c] > 1 ? 1u << 16 : 0u;
+            std::vector<int32_t> qptr((size_t)Vq + 1, 0), qcol, tmp;
+            std::vector<uint32_t> loff((size_t)Vq * SDNR_WAVE + kPad, 0u);
+            std::vector<uint8_t> mslot;
+            for (int32_t c = 0; c < Vq; ++c) {
+                const int32_t P = (int32_t)(info[c] & 0xFFFFu);
+                tmp.clear();
+                for (int32_t e = row_ptr[P]; e < row_ptr[P + 1]; ++e)
+                    tmp.push_back((int32_t)(cidrk[col[e]] & 0xFFFFu));
+                std::sort(tmp.begin(), tmp.end());
+                tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
+                for (size_t j = 0; j < tmp.size(); ++j) {
+                    loff[(size_t)c * SDNR_WAVE + j] = (uint32_t)mslot.size();
+                    mslot.resize(mslot.size() + csize[tmp[j]], 0);
+                }
+                for (int32_t e = row_ptr[P]; e < row_ptr[P + 1]; ++e) {
+                    const uint32_t ck = cidrk[col[e]];
+                    const size_t j = (size_t)(std::lower_bound(tmp.begin(), tmp.end(),
+                                                               (int32_t)(ck & 0xFFFFu)) - tmp.begin());
+                    mslot[loff[(size_t)c * SDNR_WAVE + j] + (ck >> 16)] = (uint8_t)(e - row_ptr[P]);
+                }
+                qcol.insert(qcol.end(), tmp.begin(), tmp.end());
+                qptr[(size_t)c + 1] = (int32_t)qcol.size();
+            }
+            mslot.resize(mslot.size() + kPad, 0);
+            qcol.push_back(0);                                          // never empty
+            std::vector<uint16_t> qa16, qr16;
+            bool qsym = true;
+            int32_t qmaxin = 0;
+            U16Rows q;
+            he = upload_u16_rows(q, Vq, qptr.data(), qcol.data(), qa16, qr16, qsym, qmaxin,
+                                 ctx->radj_pair ? 1 : 0);
+            ctx->q_adj16 = q.adj16;
+            ctx->q_radj16 = q.radj16;
+            ctx->q_deg32 = q.deg32;
+            ctx->q_radjw = q.radjw;
+            ctx->q_radjc = q.radjc;
+            ctx->q_radj_owned = q.radj_owned;
+            auto put = [&](void **dst, const void *src, size_t bytes) {
+                if (he == hipSuccess) he = hipMalloc(dst, bytes);
+                if (he == hipSuccess)
+                    he = hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, ctx->stream);
+            };
+            put(reinterpret_cast<void **>(&ctx->q_cid), cidrk.data(), cidrk.size() * 4);
+            put(reinterpret_cast<void **>(&ctx->q_info), info.data(), info.size() * 4);
+            put(reinterpret_cast<void **>(&ctx->q_loff), loff.data(), loff.size() * 4);
+            put(reinterpret_cast<void **>(&ctx->q_slot), mslot.data(), mslot.size());
+            const sdnr_quot qt{V, ctx->q_cid, ctx->q_info, ctx->q_loff, ctx->q_slot};
+            put(reinterpret_cast<void **>(&ctx->q_tab), &qt, sizeof qt);
+            if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
+            if (he != hipSuccess) {
+                free_graph(ctx);
+                return sdnr_hip_fail(he, "graph_upload(quotient)");
+            }
+            // a pre-swizzled form the graph lacks is not used for the quotient either
+            if (!ctx->radjw && ctx->q_radjw) {
+                (void)hipFree(ctx->q_radjw);
+                ctx->q_radjw = nullptr;
+            }
+            if (!ctx->radjc && ctx->q_radjc) {
+                (void)hipFree(ctx->q_radjc);
+                ctx->q_radjc = nullptr;
+            }
+            ctx->q_V = Vq;
+            ctx->q_E = qptr[(size_t)Vq];
         }
     }
     // symmetric (every link has its reverse): in-rows equal out-rows, so a
@@ -1946,6 +2074,14 @@ int sdnr_last_dfs_form(const sdnr_ctx *ctx, int32_t *form)
     CHECK_CTX(ctx);
     if (!form) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_last_dfs_form: null out");
     *form = ctx->dfs_form;
+    return SDNR_OK;
+}
+
+int sdnr_last_dfs_quotient(const sdnr_ctx *ctx, int32_t *on)
+{
+    CHECK_CTX(ctx);
+    if (!on) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_last_dfs_quotient: null out");
+    *on = ctx->dfs_quotient ? 1 : 0;
     return SDNR_OK;
 }
 

@@ -44,6 +44,15 @@ __device__ __forceinline__ int lds_swz(int x) { return x ^ ((x >> 3) & 31); }
 
 constexpr int kLiveRing = 8;           // runs of folded launches whose published count is still told apart
 
+// what dfs_async_kernel expands a twin-class quotient's records with (one
+// device word block, so the kernel carries one pointer through its search):
+// VR the graph's vertex count, the rest sdnr_ctx's q_cid .. q_slot
+struct sdnr_quot {
+    int32_t VR;
+    const uint32_t *cid, *info, *loff;
+    const uint8_t *slot;
+};
+
 struct sdnr_ctx {
     int device = 0;
     int num_cus = 256;
@@ -97,6 +106,23 @@ struct sdnr_ctx {
     // member per class and derives the others (sdnr_launch_dfs)
     int32_t *twin_rep = nullptr;
     bool has_twins = false;             // some class has more than one member
+    // the twin-class quotient (built with the u16 rows of a
+    // graph with twins): its vertices are the classes, numbered by ascending
+    // largest member, and dfs_async_kernel searches it in place of the graph.
+    // q_adj16 .. q_radjc are the quotient's rows in the layouts of adj16 ..
+    // radjc (paired exactly when the graph's are); q_cid[v] = class of v |
+    // rank of v in its class << 16; q_info[c] = largest member | (more than
+    // one member) << 16; q_slot[q_loff[c * 64 + j] + r] = the slot, in the
+    // out-row of c's members, of the member of rank r of the class in slot j
+    // of c's quotient row
+    int32_t q_V = 0, q_E = 0;
+    uint16_t *q_adj16 = nullptr, *q_radj16 = nullptr, *q_radjw = nullptr, *q_radjc = nullptr;
+    uint32_t *q_deg32 = nullptr;
+    bool q_radj_owned = false;
+    uint32_t *q_cid = nullptr, *q_info = nullptr, *q_loff = nullptr;
+    uint8_t *q_slot = nullptr;
+    struct sdnr_quot *q_tab = nullptr;  // the expansion tables as the kernel takes them (device)
+    bool dfs_quotient = false;          // the last DFS launch searched the quotient
     // the last DFS launch on this context: its batch size, and whether it
     // folded (then the searched count is the int at the head of scratch3)
     int32_t dfs_nsrc = 0;

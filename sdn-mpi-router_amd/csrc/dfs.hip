@@ -1699,16 +1699,28 @@ __device__ __forceinline__ int swz(int x) { return lds_swz(x); }   // common.h
 // low-load (<= 2 sources per CU) kernel ~8 us at k=48 even when the flag is
 // off (144 sources 44.3 vs 52.0 us, same box, gpurun_out/r5_abr4), while at
 // the headline's load the pop itself gains
-template <int NW, bool HOPS, bool PACKED, bool C16, int PAIR, bool SPEC = false>
+template <int NW, bool HOPS, bool PACKED, bool C16, int PAIR, bool SPEC = false, bool QUOT = false>
 __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
     int V, const uint16_t *__restrict__ adj, const uint16_t *__restrict__ radj,
     const uint32_t *__restrict__ deg, const int32_t *__restrict__ row_ptr,
     const int32_t *__restrict__ port, int W, const int32_t *__restrict__ ell_port,
     const int32_t *__restrict__ src, int nsrc, int32_t *__restrict__ out_parent,
     int32_t *__restrict__ out_port, int32_t *__restrict__ out_hops, int *__restrict__ err,
-    int flags, const int32_t *__restrict__ live)
+    int flags, const int32_t *__restrict__ live,
+    // QUOT, the twin-class quotient: V, adj, radj and deg
+    // are the quotient's, qt->VR the graph's vertex count -- the length of a
+    // table row --, and the tables are expanded in the flush: cid[v] = class
+    // | rank << 16, info[c] = largest member | twins << 16, slot[loff[c * 64
+    // + slot] + rank] the tree link's slot in the real row.  A separate
+    // instantiation: as a runtime branch its pointers cost every form
+    // registers (scalar spills 5 -> 32, the plain 4-wave forms 6 -> 5 waves
+    // per SIMD by the compiler's resource remarks), the graph's own search
+    // among them; one pointer, so the search loop carries two more scalars
+    const sdnr_quot *__restrict__ qt)
 {
     static_assert(NW >= 2, "wave 0 searches, the others decrement");
+    constexpr bool quot = QUOT;
+    const int VT = quot ? uniform((int)qt->VR) : V;   // entries of a table row
     // the twin fold's live count (device memory: the host does not know it):
     // only src[0 .. *live) is searched, no row is written behind it
     if (live) nsrc = min(nsrc, *live);
@@ -1792,17 +1804,26 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
 #endif
 
     for (int si = blockIdx.x; si < nsrc; si += gridDim.x) {
-        const int s = uniform(src[si]);
-        int32_t *prow = out_parent + (size_t)si * V;
-        int32_t *trow = PACKED ? nullptr : out_port + (size_t)si * V;
-        const size_t hb = (size_t)si * V;        // row of the hop table
-        if (s < 0 || s >= V) {
-            for (int v = threadIdx.x; v < V; v += blockDim.x) {
+        const int sr = uniform(src[si]);         // the source as the caller names it
+        int32_t *prow = out_parent + (size_t)si * VT;
+        int32_t *trow = PACKED ? nullptr : out_port + (size_t)si * VT;
+        const size_t hb = (size_t)si * VT;       // row of the hop table
+        if (sr < 0 || sr >= VT) {
+            for (int v = threadIdx.x; v < VT; v += blockDim.x) {
                 prow[v] = -1;                    // packed: 0xFFFFFFFF
                 if (!PACKED) trow[v] = -1;
                 if (HOPS) put_hop(out_hops, hb + v, -1, flags);
             }
             continue;
+        }
+        // the vertex searched from: the source, or its class in the quotient.
+        // A class of several members is explored first but not marked: the
+        // other members are pushed by whoever has the class in their row
+        int s = sr;
+        bool rootvis = true;
+        if constexpr (quot) {
+            s = uniform((int)(qt->cid[sr] & 0xFFFFu));
+            rootvis = uniform((int)(qt->info[s] >> 16)) == 0;
         }
 #ifdef SDNR_STAMPS
         unsigned long long ph0, ph1, ph2, ph3;
@@ -1850,18 +1871,19 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
         if (w == 0) {
             // ------------------------------------------------ the search
             if (flags & kFlagPrio) __builtin_amdgcn_s_setprio(3);
+            const int pub0 = rootvis ? 1 : 0;
             if (lane == 0) {
-                vis[s >> 5] |= 1u << (s & 31);
+                if (rootvis) vis[s >> 5] |= 1u << (s & 31);
                 vis[V >> 5] |= 1u << (V & 31);
                 if (C16) ps16[swz(s)] = (uint16_t)s;
                 else ps[swz(s)] = (uint32_t)s;
                 if (HOPS) dep[s] = 0;
                 stk[0] = (uint16_t)s;
-                ring[0] = (uint16_t)s;           // s's in-neighbours lose one
+                ring[0] = (uint16_t)s;           // s's in-neighbours lose one (rootvis)
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            if (lane == 0) __hip_atomic_store(&ctl[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            int pub = 1, pubd = 1, sp = 1, lo = 0;       // published / announced
+            if (lane == 0) __hip_atomic_store(&ctl[0], pub0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            int pub = pub0, pubd = pub0, sp = 1, lo = 0; // published / announced
             constexpr int NPF = 1;        // rows of the NPF largest children in flight
             // the prefetched rows stay u16 across the loop back-edge: an int
             // copy there needs the load's data (s_waitcnt vmcnt(0) at the end
@@ -2175,6 +2197,76 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
         // for their acknowledgement: fewer, wider passes (k=48 at 8 waves:
         // one pass)
         constexpr int UF = SDNR_ASYNC_FLUSH_U;
+        // the quotient's records expanded to the graph's vertices: v takes
+        // the record of its class (the root marker for the source itself);
+        // the real parent is the source where the pusher is the source's
+        // class, else the pusher's largest member, and the real slot comes
+        // from the slot table.  Each stage's gathers of all UF vertices are
+        // in flight together, and all of them before the stores
+        if constexpr (quot) {
+            const uint32_t *__restrict__ qcid = qt->cid, *__restrict__ qinfo = qt->info,
+                                         *__restrict__ qloff = qt->loff;
+            const uint8_t *__restrict__ qslot = qt->slot;
+            for (int v0 = threadIdx.x; v0 < VT; v0 += UF * blockDim.x) {
+                uint32_t ck[UF], lf[UF];
+                int p[UF], sl[UF], pt[UF];
+#pragma unroll
+                for (int k = 0; k < UF; ++k) {
+                    const int v = v0 + k * (int)blockDim.x;
+                    ck[k] = qcid[v < VT ? v : 0];
+                }
+#pragma unroll
+                for (int k = 0; k < UF; ++k) {
+                    const int v = v0 + k * (int)blockDim.x;
+                    const int c = (int)(ck[k] & 0xFFFFu);
+                    p[k] = -1;
+                    sl[k] = -1;
+                    lf[k] = 0;
+                    if (v < VT && v == sr) {
+                        p[k] = sr;
+                    } else if (v < VT && ((vis[c >> 5] >> (c & 31)) & 1u)) {
+                        int pc, qs;
+                        if (C16) {
+                            pc = (int)ps16[swz(c)];
+                            qs = (int)sl8[swz(c)];
+                        } else {
+                            const uint32_t xx = ps[swz(c)];
+                            pc = (int)(xx & 0xFFFFu);
+                            qs = (int)(xx >> 16);
+                        }
+                        p[k] = pc == s ? sr : (int)(qinfo[pc] & 0xFFFFu);
+                        lf[k] = qloff[(size_t)pc * 64 + qs];
+                        sl[k] = 0;               // a tree link: its slot is looked up below
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < UF; ++k)
+                    if (sl[k] >= 0) sl[k] = (int)qslot[lf[k] + (ck[k] >> 16)];
+#pragma unroll
+                for (int k = 0; k < UF; ++k) {
+                    pt[k] = -1;
+                    if (sl[k] >= 0)
+                        pt[k] = W > 0 ? ell_port[(size_t)p[k] * W + sl[k]]
+                                      : port[row_ptr[p[k]] + sl[k]];
+                }
+#pragma unroll
+                for (int k = 0; k < UF; ++k) {
+                    const int v = v0 + k * (int)blockDim.x;
+                    if (v < VT) {
+                        if (PACKED) {
+                            prow[v] = (int32_t)(((uint32_t)p[k] & 0xFFFFu) |
+                                                ((uint32_t)pt[k] << 16));
+                        } else {
+                            prow[v] = p[k];
+                            trow[v] = pt[k];
+                        }
+                        if (HOPS)
+                            put_hop(out_hops, hb + v,
+                                    p[k] < 0 ? -1 : (v == sr ? 0 : (int)dep[ck[k] & 0xFFFFu]), flags);
+                    }
+                }
+            }
+        } else
         for (int v0 = threadIdx.x; v0 < V; v0 += UF * blockDim.x) {
             int p[UF], sl[UF], pt[UF];
 #pragma unroll
@@ -2721,17 +2813,17 @@ static bool dfs_bits_default(const char *force)
 
 // the async kernel for a row form: compact LDS (C16), paired in-rows,
 // dword-paired in-rows, or plain u16 in-rows
-template <int N_, bool H_, bool P_, bool SPEC>
+template <int N_, bool H_, bool P_, bool SPEC, bool Q_ = false>
 static auto async_pick(bool c16, bool pair, bool dw)
 {
     // (SPEC: the plain-row kernel only -- the compact / paired forms, the
     // dragonfly's, measured slower with the speculative pop compiled in:
     // 2,064 sources 177.3 -> 180.4 us, gpurun_out/r5_abspec)
-    return c16 ? (pair ? dfs_async_kernel<N_, H_, P_, true, 1>
-                       : dfs_async_kernel<N_, H_, P_, true, 0>)
-               : (pair ? dfs_async_kernel<N_, H_, P_, false, 1>
-                       : (dw ? dfs_async_kernel<N_, H_, P_, false, 2>
-                             : dfs_async_kernel<N_, H_, P_, false, 0, SPEC>));
+    return c16 ? (pair ? dfs_async_kernel<N_, H_, P_, true, 1, false, Q_>
+                       : dfs_async_kernel<N_, H_, P_, true, 0, false, Q_>)
+               : (pair ? dfs_async_kernel<N_, H_, P_, false, 1, false, Q_>
+                       : (dw ? dfs_async_kernel<N_, H_, P_, false, 2, false, Q_>
+                             : dfs_async_kernel<N_, H_, P_, false, 0, SPEC, Q_>));
 }
 
 // hop counts as u16 (0xFFFF unreached) into d_hops
@@ -2776,6 +2868,23 @@ static bool dfs_async(const sdnr_ctx *ctx, int nsrc, bool hops)
     return dfs_count_ok(ctx, hops) &&
            dfs_lds_bytes_async(ctx->V, hops) <= SDNR_MAX_LDS_PER_BLOCK &&
            (force ? !strcmp(force, "async") : dfs_small(ctx, nsrc));
+}
+
+// search the twin-class quotient (ctx->q_*, capi.hip) in
+// place of the graph?  Only a graph with twins has one, and by default it is
+// taken when it has at most half the graph's links: below that the search
+// saves little and the flush's two extra gathers per vertex are not paid for
+// (a fat tree's quotient has 1 / k of the links; a graph with one pair of
+// twins stays on its own rows).  SDNROUTE_DFS_QUOTIENT=0|1 forces it off / on
+// (A/B, tests on graphs under the rule)
+static bool dfs_quotient(const sdnr_ctx *ctx)
+{
+    if (!ctx->q_tab || ctx->q_V <= 0) return false;
+    if (const char *f = getenv("SDNROUTE_DFS_QUOTIENT")) {
+        if (!strcmp(f, "0")) return false;
+        if (!strcmp(f, "1")) return true;
+    }
+    return 2 * (int64_t)ctx->q_E <= (int64_t)ctx->E;
 }
 
 // what the low-load form of the folded 4-wave search changes (A/B builds:
@@ -2911,7 +3020,14 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
         };
         // pre-swizzled worker rows (SDNROUTE_DFS_PRESWZ=0 keeps the plain ones)
         const char *pz = getenv("SDNROUTE_DFS_PRESWZ");
-        auto rows_of = [&](bool c) { return c ? ctx->radjc : ctx->radjw; };
+        // the search runs on the twin-class quotient where that is worth
+        // taking (dfs_quotient): the quotient's rows in every form the
+        // graph's come in, so all the rules below read as they do without it
+        const bool quot = dfs_quotient(ctx);
+        ctx->dfs_quotient = quot;
+        auto rows_of = [&](bool c) {
+            return quot ? (c ? ctx->q_radjc : ctx->q_radjw) : (c ? ctx->radjc : ctx->radjw);
+        };
         auto preswz_of = [&](bool c) { return rows_of(c) && !(pz && !strcmp(pz, "0")); };
         // the wave count: the caller's nsrc selects it, or -- the folded
         // search in its low-load form, taken from a published live count --
@@ -2971,14 +3087,19 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
 #define SDNR_ASYNC_P(N_, H_, P_)                                                             \
     do {                                                                                     \
         constexpr bool kSpecOk = N_ == 4;              /* the k=48 headline's regime */      \
-        auto k = spec && kSpecOk ? async_pick<N_, H_, P_, kSpecOk>(c16, pair, dw)            \
-                                 : async_pick<N_, H_, P_, false>(c16, pair, dw);             \
+        auto k = quot ? (spec && kSpecOk ? async_pick<N_, H_, P_, kSpecOk, true>(c16, pair, dw) \
+                                         : async_pick<N_, H_, P_, false, true>(c16, pair, dw)) \
+                      : (spec && kSpecOk ? async_pick<N_, H_, P_, kSpecOk>(c16, pair, dw)    \
+                                         : async_pick<N_, H_, P_, false>(c16, pair, dw));    \
         allow_full_lds(k);                                                                   \
-        hipLaunchKernelGGL(k, dim3(cgrid), dim3(N_ * 64), cl, ctx->stream, V, ctx->adj16,    \
-                           preswz ? rw : ctx->radj16, ctx->deg32, ctx->row_ptr,              \
+        hipLaunchKernelGGL(k, dim3(cgrid), dim3(N_ * 64), cl, ctx->stream,                   \
+                           quot ? ctx->q_V : V, quot ? ctx->q_adj16 : ctx->adj16,            \
+                           preswz ? rw : (quot ? ctx->q_radj16 : ctx->radj16),               \
+                           quot ? ctx->q_deg32 : ctx->deg32, ctx->row_ptr,                   \
                            ctx->port, ctx->W, ctx->ell_port, d_src, nsrc,                    \
                            P_ ? reinterpret_cast<int32_t *>(d_tree) : d_parent, d_port,      \
-                           d_hops, err, aflags, d_live);                                     \
+                           d_hops, err, aflags, d_live,                                      \
+                           quot ? ctx->q_tab : static_cast<const sdnr_quot *>(nullptr));     \
     } while (0)
 #define SDNR_ASYNC(N_, H_) SDNR_ASYNC_P(N_, H_, false)
         if (packed) {
@@ -3640,6 +3761,7 @@ int sdnr_launch_dfs(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
     ctx->dfs_nsrc = nsrc;
     ctx->dfs_folded = false;
     ctx->dfs_form = kDfsFormFull;
+    ctx->dfs_quotient = false;
     if (nsrc == 0 || V == 0 || !dfs_fold(ctx, nsrc))
         return dfs_dispatch(ctx, d_src, nsrc, d_parent, d_port, d_hops, d_tree, slots, hops16);
     const bool packed = d_tree != nullptr;

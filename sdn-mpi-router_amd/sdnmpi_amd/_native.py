@@ -50,7 +50,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_edge_ports", "sdnr_dfs_rows_affected", "sdnr_link_loads",
     "sdnr_ecmp_link_loads", "sdnr_graph_costs", "sdnr_cost_tables",
     "sdnr_cost_ecmp_link_loads", "sdnr_graph_twin_reps", "sdnr_last_dfs_searched",
-    "sdnr_last_dfs_form",
+    "sdnr_last_dfs_form", "sdnr_last_dfs_quotient",
     "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables", "sdnr_whatif_ecmp_link_loads",
     "sdnr_widest_tables", "sdnr_fair_rates", "sdnr_ecmp_fair_rates",
 )
@@ -126,6 +126,7 @@ def _bind(L):
         "sdnr_graph_twin_reps": ([vp, vp], c_int),
         "sdnr_last_dfs_searched": ([vp, ctypes.POINTER(i32)], c_int),
         "sdnr_last_dfs_form": ([vp, ctypes.POINTER(i32)], c_int),
+        "sdnr_last_dfs_quotient": ([vp, ctypes.POINTER(i32)], c_int),
     }
     # an A/B build named by SDNROUTE_LIB may predate some entry points: those
     # stay unbound (calling one raises AttributeError); the in-tree library
@@ -742,6 +743,13 @@ class Context(object):
         n = ctypes.c_int32()
         _check(self._lib.sdnr_last_dfs_form(self._h, ctypes.byref(n)))
         return "low" if n.value else "full"
+
+    def last_dfs_quotient(self):
+        """1 when the search kernel of the last DFS table call ran on the
+        twin-class quotient, else 0 (sdnr_last_dfs_quotient)."""
+        n = ctypes.c_int32()
+        _check(self._lib.sdnr_last_dfs_quotient(self._h, ctypes.byref(n)))
+        return n.value
 
     def last_sweeps(self):
         """Bellman-Ford sweeps of the last APSP call (sdnr_last_sweeps)."""
