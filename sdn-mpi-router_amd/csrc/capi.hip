@@ -197,7 +197,7 @@ static void free_graph(sdnr_ctx *c)
                        reinterpret_cast<void **>(&c->q_radjw), reinterpret_cast<void **>(&c->q_radjc),
                        reinterpret_cast<void **>(&c->q_cid), reinterpret_cast<void **>(&c->q_info),
                        reinterpret_cast<void **>(&c->q_loff), reinterpret_cast<void **>(&c->q_slot),
-                       reinterpret_cast<void **>(&c->q_tab)};
+                       reinterpret_cast<void **>(&c->q_port), reinterpret_cast<void **>(&c->q_tab)};
         for (void **b : qb) {
             if (*b) (void)hipFree(*b);
             *b = nullptr;
@@ -924,6 +924,7 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
             std::vector<int32_t> qptr((size_t)Vq + 1, 0), qcol, tmp;
             std::vector<uint32_t> loff((size_t)Vq * SDNR_WAVE + kPad, 0u);
             std::vector<uint8_t> mslot;
+            std::vector<int32_t> mport;                                 // the same links' ports
             for (int32_t c = 0; c < Vq; ++c) {
                 const int32_t P = (int32_t)(info[c] & 0xFFFFu);
                 tmp.clear();
@@ -934,17 +935,20 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
                 for (size_t j = 0; j < tmp.size(); ++j) {
                     loff[(size_t)c * SDNR_WAVE + j] = (uint32_t)mslot.size();
                     mslot.resize(mslot.size() + csize[tmp[j]], 0);
+                    mport.resize(mslot.size(), -1);
                 }
                 for (int32_t e = row_ptr[P]; e < row_ptr[P + 1]; ++e) {
                     const uint32_t ck = cidrk[col[e]];
                     const size_t j = (size_t)(std::lower_bound(tmp.begin(), tmp.end(),
                                                                (int32_t)(ck & 0xFFFFu)) - tmp.begin());
                     mslot[loff[(size_t)c * SDNR_WAVE + j] + (ck >> 16)] = (uint8_t)(e - row_ptr[P]);
+                    mport[loff[(size_t)c * SDNR_WAVE + j] + (ck >> 16)] = port[e];
                 }
                 qcol.insert(qcol.end(), tmp.begin(), tmp.end());
                 qptr[(size_t)c + 1] = (int32_t)qcol.size();
             }
             mslot.resize(mslot.size() + kPad, 0);
+            mport.resize(mslot.size(), -1);
             qcol.push_back(0);                                          // never empty
             std::vector<uint16_t> qa16, qr16;
             bool qsym = true;
@@ -967,7 +971,8 @@ static int graph_upload_one(sdnr_ctx *ctx, int32_t V, int32_t E, const int32_t *
             put(reinterpret_cast<void **>(&ctx->q_info), info.data(), info.size() * 4);
             put(reinterpret_cast<void **>(&ctx->q_loff), loff.data(), loff.size() * 4);
             put(reinterpret_cast<void **>(&ctx->q_slot), mslot.data(), mslot.size());
-            const sdnr_quot qt{V, ctx->q_cid, ctx->q_info, ctx->q_loff, ctx->q_slot};
+            put(reinterpret_cast<void **>(&ctx->q_port), mport.data(), mport.size() * 4);
+            const sdnr_quot qt{V, ctx->q_cid, ctx->q_info, ctx->q_loff, ctx->q_slot, ctx->q_port};
             put(reinterpret_cast<void **>(&ctx->q_tab), &qt, sizeof qt);
             if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
             if (he != hipSuccess) {

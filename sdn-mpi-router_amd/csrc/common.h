@@ -46,11 +46,12 @@ constexpr int kLiveRing = 8;           // runs of folded launches whose publishe
 
 // what dfs_async_kernel expands a twin-class quotient's records with (one
 // device word block, so the kernel carries one pointer through its search):
-// VR the graph's vertex count, the rest sdnr_ctx's q_cid .. q_slot
+// VR the graph's vertex count, the rest sdnr_ctx's q_cid .. q_port
 struct sdnr_quot {
     int32_t VR;
     const uint32_t *cid, *info, *loff;
     const uint8_t *slot;
+    const int32_t *qport;
 };
 
 struct sdnr_ctx {
@@ -114,13 +115,16 @@ struct sdnr_ctx {
     // rank of v in its class << 16; q_info[c] = largest member | (more than
     // one member) << 16; q_slot[q_loff[c * 64 + j] + r] = the slot, in the
     // out-row of c's members, of the member of rank r of the class in slot j
-    // of c's quotient row
+    // of c's quotient row, and q_port[the same index] that link's port -- the
+    // slot table composed with the port row of c's largest member, so the
+    // flush takes a tree link's port in one gather
     int32_t q_V = 0, q_E = 0;
     uint16_t *q_adj16 = nullptr, *q_radj16 = nullptr, *q_radjw = nullptr, *q_radjc = nullptr;
     uint32_t *q_deg32 = nullptr;
     bool q_radj_owned = false;
     uint32_t *q_cid = nullptr, *q_info = nullptr, *q_loff = nullptr;
     uint8_t *q_slot = nullptr;
+    int32_t *q_port = nullptr;
     struct sdnr_quot *q_tab = nullptr;  // the expansion tables as the kernel takes them (device)
     bool dfs_quotient = false;          // the last DFS launch searched the quotient
     // the last DFS launch on this context: its batch size, and whether it

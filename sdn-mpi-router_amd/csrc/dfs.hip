@@ -1688,6 +1688,24 @@ __global__ __launch_bounds__((NS + 1) * 64) void dfs_split_kernel(
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ int swz(int x) { return lds_swz(x); }   // common.h
 
+// the parts of the quotient's flush ("The quotient's flush";
+// A/B builds: -DSDNR_QUOT_FLUSH=n leaves some out, 0 keeps the four dependent
+// trips per vertex): 1 a tree link's port comes from the composed table
+// (sdnr_quot::qport; the root's children take their slot there and the port
+// from the root's own row, kept in LDS), 2 the workers record every pushed
+// class's offset into the slot table.  (A third part, the vertices' classes
+// loaded before the barrier that ends the search, gained nothing at the
+// headline and cost the 1,152-live row 2 us: profiles/quot_flush_ab.txt)
+#ifndef SDNR_QUOT_FLUSH
+#define SDNR_QUOT_FLUSH 3
+#endif
+
+// the quotient's tables come through pointers read from device memory
+// (sdnr_quot), which the compiler takes for generic ones: flat loads, counted
+// as LDS operations too, so every LDS wait would wait for them.  They are global
+template <class T> using gptr = const __attribute__((address_space(1))) T *;
+template <class T> __device__ __forceinline__ gptr<T> as_global(const T *p) { return (gptr<T>)p; }
+
 // PAIR: how a worker loads the pre-swizzled in-rows -- 0: one u16 row (64
 // lanes) per child; 1: rows of <= 32 entries repeated in lanes 32..63, one
 // load for two children; 2: the 64-entry rows read as 32 u32 words, lanes
@@ -1711,7 +1729,8 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
     // are the quotient's, qt->VR the graph's vertex count -- the length of a
     // table row --, and the tables are expanded in the flush: cid[v] = class
     // | rank << 16, info[c] = largest member | twins << 16, slot[loff[c * 64
-    // + slot] + rank] the tree link's slot in the real row.  A separate
+    // + slot] + rank] the tree link's slot in the real row, qport[the same
+    // index] its port.  A separate
     // instantiation: as a runtime branch its pointers cost every form
     // registers (scalar spills 5 -> 32, the plain 4-wave forms 6 -> 5 waves
     // per SIMD by the compiler's resource remarks), the graph's own search
@@ -1796,6 +1815,14 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
     };
     uint16_t *ring = reinterpret_cast<uint16_t *>(ps + PWp + (HOPS ? ((V + 1) >> 1) : 0));
     int *ctl = reinterpret_cast<int *>(ring + RING);   // [0] published [1] done [2+k] consumed
+    // QUOT: qlo[c] = the slot-table offset of the link class c was pushed
+    // over, written by the worker that drains c from the ring and used by the
+    // flush where vis[c] is set and nowhere else (a word of an earlier source
+    // is never used: every marked class but the root's own went through the
+    // ring); rport = the port row of the source itself (its children's ports)
+    constexpr bool qf_port = quot && (SDNR_QUOT_FLUSH & 1), qf_rec = quot && (SDNR_QUOT_FLUSH & 2);
+    uint32_t *qlo = reinterpret_cast<uint32_t *>(ctl + 16);
+    int32_t *rport = reinterpret_cast<int32_t *>(qlo + ((V + 3) & ~3));
     const int lane = lane_id();
     const int w = uniform((int)(threadIdx.x >> 6));
 #ifdef SDNR_STAMPS
@@ -1829,6 +1856,13 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
         unsigned long long ph0, ph1, ph2, ph3;
         SDNR_STAMP(ph0);
 #endif
+        // the source's own port row, beside the counts' loads (both port
+        // arrays carry a wave of padding behind the last row)
+        int rp0 = -1;
+        if constexpr (qf_port) {
+            if (w == NW - 1)
+                rp0 = W > 0 ? ell_port[(size_t)sr * W + lane] : port[row_ptr[sr] + lane];
+        }
         for (int i = threadIdx.x; i < VW; i += blockDim.x) vis[i] = 0u;
         // counts start at the out-degrees: U independent loads per thread in
         // flight before the LDS stores
@@ -1863,6 +1897,9 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
             }
         }
         if (threadIdx.x < 2 + S) ctl[threadIdx.x] = 0;
+        if constexpr (qf_port) {
+            if (w == NW - 1) rport[lane] = rp0;
+        }
         __syncthreads();
 #ifdef SDNR_STAMPS
         SDNR_STAMP(ph1);
@@ -2096,6 +2133,8 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
         } else {
             // ------------------------------------------------ the decrements
             int j = w - 1;                       // next child index of this worker
+            gptr<uint32_t> wloff = nullptr;
+            if constexpr (qf_rec) wloff = as_global(qt->loff);
             for (unsigned spin = 0;;) {
                 const int P = __hip_atomic_load(&ctl[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 if (j >= P) {
@@ -2112,6 +2151,22 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
                 spin = 0;
                 const int n = (P - j + S - 1) / S < G ? (P - j + S - 1) / S : G;
                 const int mine = lane < n ? (int)ring[(j + lane * S) & (RING - 1)] : V;
+                // QUOT: the class's record is final at its push (the search
+                // wave wrote it before the ring entry), so the slot-table
+                // offset of its tree link is loaded here, off the search's
+                // chain, beside the in-rows, and kept for the flush; the root's
+                // own entry (index 0 of a marked root) has no link
+                uint32_t qo = 0u;
+                bool qrec = false;
+                if constexpr (qf_rec) {
+                    qrec = lane < n && (j + lane * S > 0 || !rootvis);
+                    if (qrec) {
+                        uint32_t xx;
+                        if (C16) xx = (uint32_t)ps16[swz(mine)] | ((uint32_t)sl8[swz(mine)] << 16);
+                        else xx = ps[swz(mine)];
+                        qo = wloff[(size_t)(xx & 0xFFFFu) * 64 + (xx >> 16)];
+                    }
+                }
                 if constexpr (PAIR == 2) {
                     constexpr int G2 = G / 2;
                     const int hiw = lane >> 5;
@@ -2128,6 +2183,9 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
                             atomicSub(&cnt[r[g] & 0xFFFFu], 1u);
                             atomicSub(&cnt[r[g] >> 16], 1u);
                         }
+                    if constexpr (qf_rec) {
+                        if (qrec) qlo[mine] = qo;
+                    }
                     j += n * S;
                     if (lane == 0) __hip_atomic_store(&ctl[2 + w - 1], j, __ATOMIC_RELAXED,
                                                       __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2152,6 +2210,9 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
                             if (C16) atomicSub(&cnt[r[g] >> 1], 1u << ((r[g] & 1) << 4));
                             else atomicSub(&cnt[r[g]], 1u);
                         }
+                    if constexpr (qf_rec) {
+                        if (qrec) qlo[mine] = qo;
+                    }
                     j += n * S;
                     if (lane == 0) __hip_atomic_store(&ctl[2 + w - 1], j, __ATOMIC_RELAXED,
                                                       __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2181,6 +2242,9 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
                             else atomicSub(&cnt[swz(r[g])], 1u);
                         }
                 }
+                if constexpr (qf_rec) {
+                    if (qrec) qlo[mine] = qo;
+                }
                 j += n * S;
                 if (lane == 0) __hip_atomic_store(&ctl[2 + w - 1], j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
@@ -2200,16 +2264,29 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
         // the quotient's records expanded to the graph's vertices: v takes
         // the record of its class (the root marker for the source itself);
         // the real parent is the source where the pusher is the source's
-        // class, else the pusher's largest member, and the real slot comes
-        // from the slot table.  Each stage's gathers of all UF vertices are
-        // in flight together, and all of them before the stores
+        // class, else the pusher's largest member.  After the coalesced load
+        // of v's class, the record and the offset the workers kept for it are
+        // in LDS, so one stage of gathers is left: the real parent, and one
+        // word at (offset + rank) -- the link's port from the composed table,
+        // or for a child of the root the dword of the slot table that holds
+        // its slot, the port then being the root's own (rport, LDS).  No
+        // branch per vertex (a branch around a gather made it wait for the one
+        // before): a vertex without a tree link gathers at index 0 of every
+        // table and drops the result -- so does the word LDS holds for a
+        // class without a mark, which may be an earlier source's.  All UF
+        // vertices' gathers are in flight together, and all before the stores.
+        // (SDNR_QUOT_FLUSH without its part 2 loads the offset in a stage of
+        // its own, without its part 1 the slot and then the port from the
+        // parent's row: the four dependent trips this replaced)
         if constexpr (quot) {
-            const uint32_t *__restrict__ qcid = qt->cid, *__restrict__ qinfo = qt->info,
-                                         *__restrict__ qloff = qt->loff;
-            const uint8_t *__restrict__ qslot = qt->slot;
+            const gptr<uint32_t> qcid = as_global(qt->cid), qinfo = as_global(qt->info),
+                                 qloff = as_global(qt->loff);
+            const gptr<uint8_t> qslot = as_global(qt->slot);
+            const gptr<int32_t> qport = as_global(qt->qport);
             for (int v0 = threadIdx.x; v0 < VT; v0 += UF * blockDim.x) {
-                uint32_t ck[UF], lf[UF];
-                int p[UF], sl[UF], pt[UF];
+                uint32_t ck[UF], lf[UF], pi[UF], val[UF];
+                int p[UF], pt[UF], hp[UF];
+                bool ok[UF], rc[UF];             // a tree link; ... from the root
 #pragma unroll
                 for (int k = 0; k < UF; ++k) {
                     const int v = v0 + k * (int)blockDim.x;
@@ -2219,35 +2296,61 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
                 for (int k = 0; k < UF; ++k) {
                     const int v = v0 + k * (int)blockDim.x;
                     const int c = (int)(ck[k] & 0xFFFFu);
-                    p[k] = -1;
-                    sl[k] = -1;
-                    lf[k] = 0;
-                    if (v < VT && v == sr) {
-                        p[k] = sr;
-                    } else if (v < VT && ((vis[c >> 5] >> (c & 31)) & 1u)) {
-                        int pc, qs;
-                        if (C16) {
-                            pc = (int)ps16[swz(c)];
-                            qs = (int)sl8[swz(c)];
-                        } else {
-                            const uint32_t xx = ps[swz(c)];
-                            pc = (int)(xx & 0xFFFFu);
-                            qs = (int)(xx >> 16);
-                        }
-                        p[k] = pc == s ? sr : (int)(qinfo[pc] & 0xFFFFu);
-                        lf[k] = qloff[(size_t)pc * 64 + qs];
-                        sl[k] = 0;               // a tree link: its slot is looked up below
+                    const uint32_t vw = vis[c >> 5];
+                    uint32_t xx;
+                    if (C16) xx = (uint32_t)ps16[swz(c)] | ((uint32_t)sl8[swz(c)] << 16);
+                    else xx = ps[swz(c)];
+                    uint32_t off = 0u;
+                    if (qf_rec) off = qlo[c];
+                    int d = 0;
+                    if (HOPS) d = (int)dep[c];
+                    ok[k] = v < VT && v != sr && ((vw >> (c & 31)) & 1u);
+                    const int pc = ok[k] ? (int)(xx & 0xFFFFu) : 0;
+                    rc[k] = ok[k] && pc == s;
+                    p[k] = pc;
+                    if (qf_rec) lf[k] = ok[k] ? off + (ck[k] >> 16) : 0u;
+                    else lf[k] = ok[k] ? (uint32_t)pc * 64u + (xx >> 16) : 0u;
+                    hp[k] = ok[k] ? d : (v == sr ? 0 : -1);
+                }
+                if constexpr (!qf_rec) {
+#pragma unroll
+                    for (int k = 0; k < UF; ++k) pi[k] = qinfo[p[k]];
+#pragma unroll
+                    for (int k = 0; k < UF; ++k) {
+                        const uint32_t o = qloff[lf[k]];
+                        lf[k] = ok[k] ? o + (ck[k] >> 16) : 0u;
                     }
                 }
 #pragma unroll
-                for (int k = 0; k < UF; ++k)
-                    if (sl[k] >= 0) sl[k] = (int)qslot[lf[k] + (ck[k] >> 16)];
+                for (int k = 0; k < UF; ++k) {
+                    if (qf_rec) pi[k] = qinfo[p[k]];
+                    if (qf_port) {
+                        const gptr<uint32_t> at =
+                            rc[k] ? reinterpret_cast<gptr<uint32_t>>(qslot + (lf[k] & ~3u))
+                                  : reinterpret_cast<gptr<uint32_t>>(qport + lf[k]);
+                        val[k] = *at;
+                    } else {
+                        val[k] = (uint32_t)qslot[lf[k]];
+                    }
+                }
+                // the gathered words are taken here, behind the last gather's
+                // issue (left to the compiler, the first vertex's parent load
+                // sank into the branch that uses it, behind a wait for all)
+#pragma unroll
+                for (int k = 0; k < UF; ++k) __asm__ volatile("" : "+v"(pi[k]), "+v"(val[k]));
 #pragma unroll
                 for (int k = 0; k < UF; ++k) {
-                    pt[k] = -1;
-                    if (sl[k] >= 0)
-                        pt[k] = W > 0 ? ell_port[(size_t)p[k] * W + sl[k]]
-                                      : port[row_ptr[p[k]] + sl[k]];
+                    const int v = v0 + k * (int)blockDim.x;
+                    p[k] = ok[k] ? (rc[k] ? sr : (int)(pi[k] & 0xFFFFu)) : (v == sr ? sr : -1);
+                    if (qf_port) {
+                        const int own = rport[(val[k] >> ((lf[k] & 3u) << 3)) & 63u];
+                        pt[k] = ok[k] ? (rc[k] ? own : (int)val[k]) : -1;
+                    } else {
+                        const int pp = ok[k] ? p[k] : 0;
+                        pt[k] = W > 0 ? ell_port[(size_t)pp * W + val[k]]
+                                      : port[row_ptr[pp] + (int)val[k]];
+                        pt[k] = ok[k] ? pt[k] : -1;
+                    }
                 }
 #pragma unroll
                 for (int k = 0; k < UF; ++k) {
@@ -2260,9 +2363,7 @@ __global__ __launch_bounds__(NW * 64, C16 ? 7 : 1) void dfs_async_kernel(
                             prow[v] = p[k];
                             trow[v] = pt[k];
                         }
-                        if (HOPS)
-                            put_hop(out_hops, hb + v,
-                                    p[k] < 0 ? -1 : (v == sr ? 0 : (int)dep[ck[k] & 0xFFFFu]), flags);
+                        if (HOPS) put_hop(out_hops, hb + v, hp[k], flags);
                     }
                 }
             }
@@ -2481,7 +2582,10 @@ static size_t dfs_lds_bytes_count(int V, bool hops)
     return align16(4 * (VWp + CWp + SWp) + 4 * (size_t)V + (hops ? 2 * (size_t)V : 0));
 }
 
-static size_t dfs_lds_bytes_async(int V, bool hops, bool c16 = false)
+// quot: V is a twin-class quotient's, and dfs_async_kernel keeps the words of
+// its flush behind the control words: an offset per class and the source's
+// port row (SDNR_QUOT_FLUSH)
+static size_t dfs_lds_bytes_async(int V, bool hops, bool c16 = false, bool quot = false)
 {
     const size_t VWp = (size_t)((((V + 1 + 31) >> 5) + 3) & ~3);
     const size_t CWp = (size_t)(((((c16 ? (V + 2) >> 1 : V + 1) + 31) & ~31) + 64 + 255) & ~255);
@@ -2489,7 +2593,20 @@ static size_t dfs_lds_bytes_async(int V, bool hops, bool c16 = false)
     const size_t PW = (size_t)((V + 255) & ~255);
     const size_t PWp = c16 ? PW / 2 + PW / 4 : PW;
     return align16(4 * (VWp + CWp + SWp) + 4 * PWp +
-                   (hops ? 4 * (size_t)((V + 1) >> 1) : 0) + 2 * 512 + 4 * 16);
+                   (hops ? 4 * (size_t)((V + 1) >> 1) : 0) + 2 * 512 + 4 * 16 +
+                   (quot && (SDNR_QUOT_FLUSH & 3) ? 4 * (size_t)((V + 3) & ~3) + 4 * SDNR_WAVE : 0));
+}
+
+// what a launch of dfs_async_kernel reserves: the graph's layout, also where
+// the kernel lays out the quotient's (a fat tree's is well under half of it,
+// so the flush's words cost the headline nothing); more only where a quotient
+// of nearly the graph's size does not fit that with its flush's words.  The
+// limit check and the workgroups per CU are computed from this
+static size_t dfs_async_reserve(const sdnr_ctx *ctx, bool hops, bool c16, bool quot)
+{
+    const size_t g = dfs_lds_bytes_async(ctx->V, hops, c16);
+    const size_t q = quot ? dfs_lds_bytes_async(ctx->q_V, hops, c16, true) : 0;
+    return q > g ? q : g;
 }
 
 static size_t dfs_lds_bytes_coop(int V)
@@ -2877,9 +2994,12 @@ static bool dfs_async(const sdnr_ctx *ctx, int nsrc, bool hops)
 // (a fat tree's quotient has 1 / k of the links; a graph with one pair of
 // twins stays on its own rows).  SDNROUTE_DFS_QUOTIENT=0|1 forces it off / on
 // (A/B, tests on graphs under the rule)
-static bool dfs_quotient(const sdnr_ctx *ctx)
+static bool dfs_quotient(const sdnr_ctx *ctx, bool hops)
 {
     if (!ctx->q_tab || ctx->q_V <= 0) return false;
+    // (a quotient whose layout, with its flush's words, is beyond a
+    // workgroup's LDS is none: the graph is searched on its own rows)
+    if (dfs_async_reserve(ctx, hops, false, true) > SDNR_MAX_LDS_PER_BLOCK) return false;
     if (const char *f = getenv("SDNROUTE_DFS_QUOTIENT")) {
         if (!strcmp(f, "0")) return false;
         if (!strcmp(f, "1")) return true;
@@ -3002,13 +3122,18 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
     const bool coop = !count && coop_ok && (force ? !strcmp(force, "coop") : small);
     if (async) {
         int *err = ctx->d_err;
+        // the search runs on the twin-class quotient where that is worth
+        // taking (dfs_quotient): the quotient's rows in every form the
+        // graph's come in, so all the rules below read as they do without it
+        const bool quot = dfs_quotient(ctx, hops);
+        ctx->dfs_quotient = quot;
         // workgroups per CU at w waves: LDS, and the 32 wave slots; the
         // compact layout (u16 counts, u16 parents + u8 slots) where it holds
         // more sources at once and the full layout cannot hold them all
         // (dragonfly 2,064 sources: 9 x 3 waves per CU vs 6);
         // SDNROUTE_DFS_C16=0|1 forces it
         auto per_cu = [&](int w, bool c) {
-            size_t b = SDNR_LDS_PER_CU / dfs_lds_bytes_async(V, hops, c);
+            size_t b = SDNR_LDS_PER_CU / dfs_async_reserve(ctx, hops, c, quot);
             if (b > (size_t)(32 / w)) b = 32 / w;
             return b < 1 ? (size_t)1 : b;
         };
@@ -3020,11 +3145,6 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
         };
         // pre-swizzled worker rows (SDNROUTE_DFS_PRESWZ=0 keeps the plain ones)
         const char *pz = getenv("SDNROUTE_DFS_PRESWZ");
-        // the search runs on the twin-class quotient where that is worth
-        // taking (dfs_quotient): the quotient's rows in every form the
-        // graph's come in, so all the rules below read as they do without it
-        const bool quot = dfs_quotient(ctx);
-        ctx->dfs_quotient = quot;
         auto rows_of = [&](bool c) {
             return quot ? (c ? ctx->q_radjc : ctx->q_radjw) : (c ? ctx->radjc : ctx->radjw);
         };
@@ -3041,7 +3161,7 @@ static int dfs_dispatch(sdnr_ctx *ctx, const int32_t *d_src, int32_t nsrc,
             if (!cc && !(preswz_of(cc) && ctx->radj_pair)) nw = cw;
         }
         const bool c16 = compact(nw);
-        const size_t cl = dfs_lds_bytes_async(V, hops, c16);
+        const size_t cl = dfs_async_reserve(ctx, hops, c16, quot);
         const size_t cpc = per_cu(nw, c16);
         const uint16_t *rw = rows_of(c16);
         const bool preswz = preswz_of(c16);
