@@ -372,6 +372,73 @@ int sdnr_link_loads(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nro
                     const int64_t *pair_off, const int32_t *dsts, const uint64_t *weight,
                     uint64_t *load, uint32_t flags);
 
+/* Multicast trees: the one-to-many flow entries of groups and the loads they
+ * put on the links.  OpenFlow 1.0 lets one flow entry carry several output
+ * actions, so a switch can replicate; when a root sends to a group along the
+ * controller's own routes, the links used are the SET UNION of the members'
+ * routes -- the (dpid, out_port) entries Router._add_flows_for_path (reference
+ * sdnmpi/router.py:83-104) would install for find_route(root, m) over the
+ * members m, each once (the reference itself can only flood one-to-many
+ * traffic, BroadcastRequest, sdnmpi/topology.py:150-177).  No route is built:
+ * one lane per member walks its route through the table row and marks the
+ * links in an E-bit map of the group (in LDS while V + E bits fit 32 KiB, else
+ * in the context scratch); the union is that map.
+ *   tree      [nrows][V] rows as sdnr_link_loads takes them: default-route
+ *             trees in layout SDNR_TREE_INT32, SDNR_TREE_PORT16 or
+ *             SDNR_TREE_SLOT; with SDNR_MCAST_TO_ROOT per-destination next-hop
+ *             rows (nh of sdnr_shortest_tables / sdnr_cost_tables, layout
+ *             SDNR_TREE_INT32 only);
+ *   root      [ngroups] int32: the root switch of group g (dense id);
+ *   mem_off   [ngroups + 1] int64: the members of group g are the pairs
+ *             (mem_row[i], mem_vertex[i]), i in mem_off[g] .. mem_off[g+1);
+ *             tree rows: mem_row[i] is the row of root[g]'s tree (the same for
+ *             every member of the group), the route climbs parent() from
+ *             mem_vertex[i] to the root and its links are parent(x) -> x;
+ *             SDNR_MCAST_TO_ROOT: mem_row[i] is the row of destination
+ *             mem_vertex[i], the route descends from root[g] along nh[mem_row[i]]
+ *             and its links are x -> nh[x];
+ *   weight    [ngroups] u64, NULL: all 1;
+ *   reached   [mem_off[ngroups]] u8, may be NULL: 1 when member i's route
+ *             exists -- tree rows: the member's own word is not SDNR_TREE_NONE
+ *             (PORT16: its parent half is not 0xFFFF); SDNR_MCAST_TO_ROOT:
+ *             nh[mem_row[i]][root[g]] >= 0 -- or when the member is the root
+ *             (no link); 0 for an unreached member and for a root, row or
+ *             vertex outside its range: these contribute nothing.  Repeated
+ *             members count as one;
+ *   ent_cnt   [ngroups] int64, may be NULL: the number of links of group g's
+ *             union (0 for a group without members);
+ *   ent_off, ent_edge  both NULL or both given: ent_off [ngroups + 1] int64 is
+ *             the caller's exclusive prefix of ent_cnt, and the union of group
+ *             g is written as int32 CSR edge ids, ascending, at ent_edge[
+ *             ent_off[g] .. ent_off[g+1]) -- a count call, the prefix sum, then
+ *             a fill call (the idiom of sdnr_route_offsets / sdnr_route_expand;
+ *             the fill walks again, nothing is kept between the calls).  A group
+ *             whose slice is not exactly its count, or leaves [ent_off[0],
+ *             ent_off[ngroups]], is not written and sdnr_synchronize reports
+ *             SDNR_ERR_INVAL;
+ *   load      [E] u64 in the CSR's edge order, may be NULL: load[e] +=
+ *             weight[g] once for every link e of group g's union.  The call
+ *             ADDS into load (pass it to one of the two calls); sums wrap,
+ *             bit-exact and order-independent.
+ * Device pointers only (flags must hold SDNR_DEVICE_PTRS); asynchronous on
+ * the context stream (the ends of mem_off and ent_off are read back first: not
+ * monotone is SDNR_ERR_INVAL); on a multi-device context it runs on the
+ * primary device.  ngroups == 0 or no members: SDNR_OK, nothing touched.
+ * Every walk is bounded by V steps.  A walk that runs out (a parent cycle),
+ * leaves [0, V), ends at a vertex that is not the root or steps over a pair
+ * that is no link of the uploaded CSR marks a row that is not a tree of the
+ * graph: sdnr_synchronize reports SDNR_ERR_INVAL, and the walk's whole group
+ * contributes nothing (count 0, no edges, no load; the walks of a group share
+ * their claims, so one walk's links cannot be taken back alone). */
+#define SDNR_MCAST_TO_ROOT 0x40u /* sdnr_multicast_trees: rows are per-destination
+                                  * next-hop rows, walked down from the root */
+int sdnr_multicast_trees(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nrows,
+                         int32_t ngroups, const int32_t *root, const int64_t *mem_off,
+                         const int32_t *mem_row, const int32_t *mem_vertex,
+                         const uint64_t *weight, uint8_t *reached, int64_t *ent_cnt,
+                         const int64_t *ent_off, int32_t *ent_edge, uint64_t *load,
+                         uint32_t flags);
+
 /* Per-link loads of a traffic matrix under ECMP: every pair's traffic is split
  * over ALL its shortest routes -- the set find_route(multiple=True) returns
  * (reference _find_routes_bfs, sdnmpi/util/topology_db.py:86-122) -- where

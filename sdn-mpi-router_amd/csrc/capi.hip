@@ -57,6 +57,12 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "uploaded graph (an ancestor chain longer than V, a parent that is "
                              "no vertex, a tree link the graph lacks) or pair_off is not "
                              "monotone: loads invalid");
+        if (h & kErrMcast)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: a row is not a tree of the "
+                             "uploaded graph (a walk longer than V, a parent or next hop that is "
+                             "no vertex, a walk that ends off the root, a link the graph lacks: "
+                             "that group adds nothing), mem_off outside the member list or "
+                             "ent_off not the prefix of the counts (that group not written)");
         if (h & kErrEcmpLoads)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_link_loads: a distance row is not a BFS "
                              "labelling of the uploaded graph (a vertex without a next hop, a "
@@ -1418,6 +1424,70 @@ int sdnr_link_loads(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nro
     ctx->timed = (flags & SDNR_TIMING) != 0;
     return sdnr_launch_link_loads(ctx, tree, layout, to_root, nrows, pair_off, lo, hi, dsts,
                                   weight, load);
+}
+
+// off[0] and off[n] of a device int64 offset array (two int64 read back)
+static int fetch_offset_ends(sdnr_ctx *ctx, const int64_t *off, int32_t n, int64_t *lo, int64_t *hi)
+{
+    int w[4];
+    int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(off), 2, w);
+    if (!rc) rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(off + n), 2, w + 2);
+    if (rc) return rc;
+    *lo = (int64_t)(((uint64_t)(uint32_t)w[1] << 32) | (uint32_t)w[0]);
+    *hi = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
+    return SDNR_OK;
+}
+
+int sdnr_multicast_trees(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nrows,
+                         int32_t ngroups, const int32_t *root, const int64_t *mem_off,
+                         const int32_t *mem_row, const int32_t *mem_vertex,
+                         const uint64_t *weight, uint8_t *reached, int64_t *ent_cnt,
+                         const int64_t *ent_off, int32_t *ent_edge, uint64_t *load,
+                         uint32_t flags)
+{
+    CHECK_CTX(ctx);
+    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_multicast_trees: no graph uploaded");
+    if (!(flags & SDNR_DEVICE_PTRS))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: device pointers only");
+    if (nrows < 0 || ngroups < 0)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: negative count");
+    if (layout != SDNR_TREE_INT32 && layout != SDNR_TREE_PORT16 && layout != SDNR_TREE_SLOT)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: layout %d", layout);
+    const bool to_root = (flags & SDNR_MCAST_TO_ROOT) != 0;
+    if (to_root && layout != SDNR_TREE_INT32)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: SDNR_MCAST_TO_ROOT takes int32 "
+                         "next-hop rows (layout %d)", layout);
+    if (layout == SDNR_TREE_PORT16 && ctx->V > 0xFFFF)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: port16 needs V <= 65535 (V=%d)",
+                         ctx->V);
+    if (layout == SDNR_TREE_SLOT && ctx->V > (1 << 26) - 1)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: slots need V < 2^26 (V=%d)",
+                         ctx->V);
+    if ((ent_off == nullptr) != (ent_edge == nullptr))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: ent_off and ent_edge go together");
+    if (ngroups == 0) return SDNR_OK;
+    if (!root || !mem_off) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: null pointer");
+    SDNR_HIP(hipSetDevice(ctx->device));
+    int64_t lo, hi, elo = 0, ehi = 0;
+    int rc = fetch_offset_ends(ctx, mem_off, ngroups, &lo, &hi);
+    if (rc) return rc;
+    if (lo < 0 || hi < lo)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: mem_off not monotone (mem_off[0]="
+                         "%lld, mem_off[%d]=%lld)", (long long)lo, ngroups, (long long)hi);
+    if (hi == lo || ctx->V == 0) return SDNR_OK;
+    if (!tree || !mem_row || !mem_vertex)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: null pointer");
+    if (ent_off) {
+        if ((rc = fetch_offset_ends(ctx, ent_off, ngroups, &elo, &ehi))) return rc;
+        if (elo < 0 || ehi < elo)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: ent_off not monotone "
+                             "(ent_off[0]=%lld, ent_off[%d]=%lld)", (long long)elo, ngroups,
+                             (long long)ehi);
+    }
+    ctx->timed = (flags & SDNR_TIMING) != 0;
+    return sdnr_launch_multicast_trees(ctx, tree, layout, to_root, nrows, ngroups, root, mem_off,
+                                       lo, hi, mem_row, mem_vertex, weight, reached, ent_cnt,
+                                       ent_off, elo, ehi, ent_edge, load);
 }
 
 int sdnr_fair_rates(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nrows,

@@ -40,6 +40,54 @@ __device__ __forceinline__ int highest_lane(uint64_t m) { return 63 - __clzll(m)
 // indexed this way are sized in whole 256-entry blocks.
 __device__ __forceinline__ int lds_swz(int x) { return x ^ ((x >> 3) & 31); }
 
+// tree / next-hop rows as sdnr_link_loads and sdnr_multicast_trees take them
+struct LoadRows {
+    const uint32_t *tree;     // [nrows][V]: int32 parents / next hops, port16 or slot words
+    int layout;               // SDNR_TREE_INT32 / SDNR_TREE_PORT16 / SDNR_TREE_SLOT
+    int to_root;              // rows are next-hop rows: the edge is v -> parent
+};
+
+// parent of v (-1: the root, an unreached vertex, or a word that names no
+// vertex of the graph -- *bad then); *slot: position of v in the parent's CSR
+// row (slot layout only)
+__device__ __forceinline__ int load_parent(const LoadRows &t, size_t rb, int v, int V, int *slot,
+                                           bool *bad)
+{
+    const uint32_t w = t.tree[rb + v];
+    int p;
+    *slot = -1;
+    if (t.layout == SDNR_TREE_PORT16) {
+        p = (int)(w & 0xFFFFu);
+        if (p == 0xFFFF) return -1;
+    } else if (t.layout == SDNR_TREE_SLOT) {
+        if (w == 0xFFFFFFFFu) return -1;
+        p = (int)(w & 0x3FFFFFFu);
+        *slot = (int)(w >> 26);
+    } else {
+        p = (int)w;
+        if (p < 0) return -1;
+    }
+    if (p == v) return -1;                        // the root of a source tree
+    if (p >= V) {
+        *bad = true;
+        return -1;
+    }
+    return p;
+}
+
+// index of the CSR entry (u, x), -1 if u has no such link
+__device__ __forceinline__ int edge_index(const int32_t *__restrict__ row_ptr,
+                                          const int32_t *__restrict__ col, int u, int x)
+{
+    int lo = row_ptr[u], hi = row_ptr[u + 1];
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (col[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return (lo < row_ptr[u + 1] && col[lo] == x) ? lo : -1;
+}
+
 // ------------------------------------------------------------------ host --
 
 constexpr int kLiveRing = 8;           // runs of folded launches whose published count is still told apart
@@ -319,6 +367,16 @@ static_assert(kEcmpFairLdsMaxV == 7400 && kEcmpFairLdsMaxV < 0xFFFF, "depths in 
 static_assert(kEcmpFairLdsMaxV * kEcmpFairBytesPerV + 16 + 512 <= SDNR_LDS_PER_CU,
               "the row state, its 16-byte rounding and the static words fit the CU's LDS");
 
+constexpr int kErrMcast = 4194304; // sdnr_multicast_trees: a row is not a tree of the graph / bad offsets
+
+// sdnr_multicast_trees keeps a group's visited map (V bits) and link map (E
+// bits) in LDS while their u32 words fit kMcastLdsBytes -- 32 KiB, so four
+// 256-thread workgroups share a CU's 160 KiB --, else in a per-workgroup slice
+// of the context's scratch (global atomics; at most kLoadsScratchBytes in all)
+constexpr size_t kMcastLdsBytes = 32 * 1024;
+static_assert(4 * kMcastLdsBytes + 4 * 1024 <= SDNR_LDS_PER_CU,
+              "four workgroups' maps and their static words fit the CU's LDS");
+
 // error plumbing (capi.hip)
 int sdnr_fail(int code, const char *fmt, ...);
 int sdnr_hip_fail(hipError_t e, const char *what);
@@ -445,5 +503,14 @@ int sdnr_launch_ecmp_fair_rates(sdnr_ctx *ctx, const uint32_t *d_pcost, int32_t 
                                 const int32_t *d_extra, const double *d_cap, int32_t nextra,
                                 double *d_rate, int32_t *d_bott, int32_t *d_round, double *d_level,
                                 int32_t max_rounds, double *d_used, int32_t *nrounds, bool hop);
+// multicast trees of groups of members over tree / next-hop rows (multicast.hip);
+// mem_lo / mem_hi = mem_off[0] / mem_off[ngroups], ent_lo / ent_hi likewise of ent_off
+int sdnr_launch_multicast_trees(sdnr_ctx *ctx, const void *d_tree, int32_t layout, bool to_root,
+                                int32_t nrows, int32_t ngroups, const int32_t *d_root,
+                                const int64_t *d_mem_off, int64_t mem_lo, int64_t mem_hi,
+                                const int32_t *d_mem_row, const int32_t *d_mem_vertex,
+                                const uint64_t *d_weight, uint8_t *d_reached, int64_t *d_ent_cnt,
+                                const int64_t *d_ent_off, int64_t ent_lo, int64_t ent_hi,
+                                int32_t *d_ent_edge, uint64_t *d_load);
 int sdnr_launch_edge_ports(sdnr_ctx *ctx, const uint64_t *d_ends, int32_t nends,
                            const uint64_t *d_ports, int32_t nports, uint8_t *d_is_edge);

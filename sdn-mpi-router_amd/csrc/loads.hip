@@ -36,53 +36,6 @@ namespace {
 
 constexpr int kLoadsThreads = 512;
 
-struct LoadRows {
-    const uint32_t *tree;     // [nrows][V]: int32 parents / next hops, port16 or slot words
-    int layout;               // SDNR_TREE_INT32 / SDNR_TREE_PORT16 / SDNR_TREE_SLOT
-    int to_root;              // rows are next-hop rows: the edge is v -> parent
-};
-
-// parent of v (-1: the root, an unreached vertex, or a word that names no
-// vertex of the graph -- *bad then); *slot: position of v in the parent's CSR
-// row (slot layout only)
-__device__ __forceinline__ int load_parent(const LoadRows &t, size_t rb, int v, int V, int *slot,
-                                           bool *bad)
-{
-    const uint32_t w = t.tree[rb + v];
-    int p;
-    *slot = -1;
-    if (t.layout == SDNR_TREE_PORT16) {
-        p = (int)(w & 0xFFFFu);
-        if (p == 0xFFFF) return -1;
-    } else if (t.layout == SDNR_TREE_SLOT) {
-        if (w == 0xFFFFFFFFu) return -1;
-        p = (int)(w & 0x3FFFFFFu);
-        *slot = (int)(w >> 26);
-    } else {
-        p = (int)w;
-        if (p < 0) return -1;
-    }
-    if (p == v) return -1;                        // the root of a source tree
-    if (p >= V) {
-        *bad = true;
-        return -1;
-    }
-    return p;
-}
-
-// index of the CSR entry (u, x), -1 if u has no such link
-__device__ __forceinline__ int edge_index(const int32_t *__restrict__ row_ptr,
-                                          const int32_t *__restrict__ col, int u, int x)
-{
-    int lo = row_ptr[u], hi = row_ptr[u + 1];
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (col[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return (lo < row_ptr[u + 1] && col[lo] == x) ? lo : -1;
-}
-
 // JT: u16 (LDS, kNone 0xFFFF) or u32 (global scratch, kNone 0xFFFFFFFF)
 template <typename JT, bool LDS>
 __global__ __launch_bounds__(kLoadsThreads) void link_loads_kernel(

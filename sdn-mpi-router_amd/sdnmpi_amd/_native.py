@@ -28,6 +28,7 @@ SAME_TABLES = 0x4        # route expansion: the previous call's parent / port ta
 LOADS_TO_ROOT = 0x8      # sdnr_link_loads: per-destination next-hop rows
 LOADS_SPLIT_HOP = 0x10   # sdnr_ecmp_link_loads: even split over a switch's next hops
 LFA_LINK_ONLY = 0x20     # sdnr_lfa_tables: link-protecting alternates only
+MCAST_TO_ROOT = 0x40     # sdnr_multicast_trees: per-destination next-hop rows
 UNREACHED = -1
 DIST_INF = 0xFFFF
 TREE_NONE = 0xFFFFFFFF
@@ -52,7 +53,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_cost_ecmp_link_loads", "sdnr_graph_twin_reps", "sdnr_last_dfs_searched",
     "sdnr_last_dfs_form", "sdnr_last_dfs_quotient",
     "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables", "sdnr_whatif_ecmp_link_loads",
-    "sdnr_widest_tables", "sdnr_fair_rates", "sdnr_ecmp_fair_rates",
+    "sdnr_widest_tables", "sdnr_fair_rates", "sdnr_ecmp_fair_rates", "sdnr_multicast_trees",
 )
 
 
@@ -110,6 +111,8 @@ def _bind(L):
         "sdnr_dfs_rows_affected": ([vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, u32], c_int),
         "sdnr_link_loads": ([vp, vp, i32, i32, vp, vp, vp, vp, u32], c_int),
         "sdnr_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, vp, u32], c_int),
+        "sdnr_multicast_trees": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                  u32], c_int),
         "sdnr_graph_costs": ([vp, vp], c_int),
         "sdnr_cost_tables": ([vp, vp, i32, vp, vp, vp, u32], c_int),
         "sdnr_cost_ecmp_link_loads": ([vp, vp, i32, vp, vp, vp, vp, u32], c_int),
@@ -501,6 +504,25 @@ class Context(object):
             ctypes.c_void_p(dsts_ptr) if dsts_ptr else None,
             ctypes.c_void_p(weight_ptr) if weight_ptr else None,
             ctypes.c_void_p(load_ptr) if load_ptr else None, flags))
+
+    def multicast_trees_device(self, tree_ptr, layout, nrows, ngroups, root_ptr, mem_off_ptr,
+                               mem_row_ptr, mem_vertex_ptr, weight_ptr=0, reached_ptr=0,
+                               ent_cnt_ptr=0, ent_off_ptr=0, ent_edge_ptr=0, load_ptr=0,
+                               to_root=False, timing=False):
+        """Multicast trees of ``ngroups`` groups over [nrows][V] tree rows
+        (``to_root``: next-hop rows, SDNR_MCAST_TO_ROOT): sdnr_multicast_trees,
+        device pointers, asynchronous.  A count call gives ``ent_cnt_ptr``
+        (int64 [ngroups]), a fill call ``ent_off_ptr`` (its exclusive prefix)
+        and ``ent_edge_ptr`` (int32 edge ids); ``load_ptr`` (u64 [E]) is ADDED
+        into by the call that gets it, ``weight_ptr`` 0: every group weighs 1;
+        ``reached_ptr``: u8 per member.  Pointers that are 0 are left out."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0) | (MCAST_TO_ROOT if to_root else 0)
+        p = [ctypes.c_void_p(x) if x else None
+             for x in (root_ptr, mem_off_ptr, mem_row_ptr, mem_vertex_ptr, weight_ptr, reached_ptr,
+                       ent_cnt_ptr, ent_off_ptr, ent_edge_ptr, load_ptr)]
+        _check(self._lib.sdnr_multicast_trees(
+            self._h, ctypes.c_void_p(tree_ptr) if tree_ptr else None, int(layout), int(nrows),
+            int(ngroups), *(p + [flags])))
 
     def ecmp_link_loads_device(self, dist_ptr, nrows, pair_off_ptr, srcs_ptr, weight_ptr,
                                load_ptr, hop=False, timing=False):

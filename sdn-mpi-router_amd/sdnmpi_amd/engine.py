@@ -50,7 +50,8 @@ __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "LFA_DOWNSTREAM", "LFA_NODE", "widest_tables_host", "check_link_utilisation", "UTIL_MAX",
            "WIDEST_LDS_MAX_V", "WIDEST_LDS_B4_MAX_V", "WIDEST_LDS_B6_MAX_V", "fair_rates_host",
            "check_fair_flows", "FAIR_LDS_MAX_V", "FAIR_MULT_LIMIT", "ecmp_fair_rates_host",
-           "ECMP_FAIR_LDS_MAX_V", "FAIR_TIE"]
+           "ECMP_FAIR_LDS_MAX_V", "FAIR_TIE", "multicast_trees_host", "MCAST_LDS_BYTES",
+           "multicast_maps_in_lds"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -337,6 +338,113 @@ def link_loads_host(csr, tree, layout, rows, dsts, weights=None, to_root=False):
         raise ValueError("link_loads_host: a tree link the graph does not have")
     np.add.at(load, e, acc[r, v])
     return load
+
+
+MCAST_LDS_BYTES = 32 * 1024     # csrc/common.h kMcastLdsBytes: the V- and E-bit maps' words in LDS
+
+
+def multicast_maps_in_lds(V, E):
+    """Whether sdnr_multicast_trees keeps a group's two bit maps in LDS."""
+    return 4 * ((int(V) + 31) // 32 + (int(E) + 31) // 32) <= MCAST_LDS_BYTES
+
+
+def multicast_trees_host(csr, tree, layout, root, mem_off, mem_row, mem_vertex, weights=None,
+                         to_root=False):
+    """numpy restatement of sdnr_multicast_trees (the CPU tests' engine double
+    and what the GPU tests compare multicast.hip against): ``(reached uint8
+    [nmem], ent_off int64 [ngroups + 1], ent_edge int32, load uint64 [E])``.
+
+    Group g has root switch ``root[g]`` and the members ``(mem_row[i],
+    mem_vertex[i])``, i in ``mem_off[g]:mem_off[g+1]``; its multicast tree is
+    the set union of the links of its members' routes -- in a tree row of the
+    root (``layout`` PORT16 / SLOT words or INT32 parents) the climb from the
+    member to the root, links parent(x) -> x; with ``to_root`` the descent
+    from the root along the member's own next-hop row (INT32), links x ->
+    nh[x].  ``ent_edge[ent_off[g]:ent_off[g+1]]`` are the union's CSR edge ids,
+    ascending; ``load[e]`` sums ``weights[g]`` (u64, None: 1; sums wrap) over
+    the groups whose union holds e.  A member is reached when its route exists
+    (its word is not none / ``nh[row][root] >= 0``) or it is the root itself;
+    roots, rows and vertices outside their ranges are unreached and contribute
+    nothing, repeated members count once.
+
+    Deliberately not the kernel's algorithm: all walks advance together one
+    hop per step, walkers that meet merge, the (group, link) pairs are
+    de-duplicated at the end with ``np.unique``.  A row that is not a tree of
+    the graph raises ValueError."""
+    V, E = int(csr.V), int(csr.E)
+    tree = np.asarray(tree)
+    nrows = int(tree.shape[0]) if tree.ndim == 2 else 0
+    root = np.asarray(root, np.int64).reshape(-1)
+    mem_off = np.asarray(mem_off, np.int64).reshape(-1)
+    row = np.asarray(mem_row, np.int64).reshape(-1)
+    vert = np.asarray(mem_vertex, np.int64).reshape(-1)
+    ng, nmem = root.shape[0], row.shape[0]
+    if mem_off.shape[0] != ng + 1 or (ng and (mem_off[0] != 0 or mem_off[-1] != nmem)) or \
+            (np.diff(mem_off) < 0).any() or vert.shape[0] != nmem:
+        raise ValueError("multicast_trees_host: mem_off is not the offsets of the members")
+    w = np.ones(ng, np.uint64) if weights is None else np.asarray(weights, np.uint64).reshape(-1)
+    if w.shape[0] != ng:
+        raise ValueError("multicast_trees_host: one weight per group")
+    reached = np.zeros(nmem, np.uint8)
+    load = np.zeros(E, np.uint64)
+    ent_off = np.zeros(ng + 1, np.int64)
+    if nmem == 0 or V == 0:
+        return reached, ent_off, np.zeros(0, np.int32), load
+    grp = np.repeat(np.arange(ng, dtype=np.int64), np.diff(mem_off))
+    r = root[grp]
+    ok = (r >= 0) & (r < V) & (row >= 0) & (row < nrows) & (vert >= 0) & (vert < V)
+    idx = np.nonzero(ok)[0]
+    g, r, rw, v = grp[idx], r[idx], row[idx], vert[idx]
+
+    def step(rows, xs):
+        """parent / next hop of xs in rows (int64, -1: none)"""
+        wd = tree[rows, xs]
+        if layout == INT32:
+            return wd.astype(np.int64)
+        return tree_parent(wd, layout)
+
+    if to_root:
+        got = (v == r) | (step(rw, r) >= 0)
+    elif layout == INT32:
+        got = (v == r) | (tree[rw, v].astype(np.int64) != -1)
+    else:
+        got = (v == r) | (tree_parent(tree[rw, v], layout) >= 0)
+    reached[idx[got]] = 1
+    act = got & (v != r)
+    g, rw = g[act], rw[act]
+    cur, end = (r[act], v[act]) if to_root else (v[act], r[act])
+    keys, _ = _edge_keys_host(csr)
+    found = []
+    for _ in range(V):
+        if cur.size == 0:
+            break
+        nxt = step(rw, cur)
+        if ((nxt < 0) | (nxt >= V)).any():
+            raise ValueError("multicast_trees_host: a walk ends off its root (not a tree row)")
+        k = cur * V + nxt if to_root else nxt * V + cur
+        e = np.minimum(np.searchsorted(keys, k), max(E, 1) - 1)
+        if E == 0 or not np.array_equal(keys[e], k):
+            raise ValueError("multicast_trees_host: a tree link the graph does not have")
+        found.append(g * E + e)
+        cur = nxt
+        keep = cur != end
+        g, rw, cur, end = g[keep], rw[keep], cur[keep], end[keep]
+        if cur.size > 1:                                   # walkers that met go on as one
+            if max(ng, 1) * max(nrows, 1) * V * V < (1 << 62):
+                _, first = np.unique(((g * nrows + rw) * V + cur) * V + end, return_index=True)
+            else:
+                _, first = np.unique(np.stack([g, rw, cur, end], 1), axis=0, return_index=True)
+            g, rw, cur, end = g[first], rw[first], cur[first], end[first]
+    else:
+        if cur.size:
+            raise ValueError("multicast_trees_host: a walk longer than V (not a tree row)")
+    if found:
+        pairs = np.unique(np.concatenate(found))
+        pg, pe = pairs // E, pairs % E
+        np.cumsum(np.bincount(pg, minlength=ng), out=ent_off[1:])
+        np.add.at(load, pe, w[pg])
+        return reached, ent_off, pe.astype(np.int32), load
+    return reached, ent_off, np.zeros(0, np.int32), load
 
 
 FAIR_LDS_MAX_V = 6800           # csrc/common.h kFairLdsMaxV: fair-rate row state in LDS up to this V
@@ -1558,6 +1666,79 @@ class RouteEngine(object):
                                    to_root=to_root, timing=timing)
         self.ctx.synchronize()              # raises if a row was not a tree
         return load.cpu().numpy().view(np.uint64)
+
+    def multicast_trees(self, export, tree, layout, root, mem_off, mem_row, mem_vertex,
+                        weights=None, to_root=False, entries=True, loads=True):
+        """Multicast trees of groups over device tree rows (multicast.hip,
+        sdnr_multicast_trees): ``(reached uint8 [nmem], ent_off int64
+        [ngroups + 1], ent_edge int32, load uint64 [E])`` in numpy, the
+        contract of :func:`multicast_trees_host`.
+
+        ``tree``: [k, V] int32 device tensor -- tree words of ``layout``
+        (PORT16 / SLOT), int32 parents (INT32) or, with ``to_root``, int32
+        next-hop rows.  A count call (which also adds the loads), the prefix
+        sum of the counts on the device, then a fill call.  ``entries=False``
+        skips the fill (``ent_edge`` is None, ``ent_off`` still the prefix of
+        the counts), ``loads=False`` the loads (``load`` is None).  The
+        kernel time of the calls made is left in ``last_multicast_ms``."""
+        self.load(export)
+        t = self._torch
+        V, E = int(export.csr.V), int(export.csr.E)
+        root = np.ascontiguousarray(root, np.int32).reshape(-1)
+        off = np.ascontiguousarray(mem_off, np.int64).reshape(-1)
+        mrow = np.ascontiguousarray(mem_row, np.int32).reshape(-1)
+        mver = np.ascontiguousarray(mem_vertex, np.int32).reshape(-1)
+        ng, nmem = root.shape[0], mrow.shape[0]
+        if off.shape[0] != ng + 1 or (ng and (off[0] != 0 or off[-1] != nmem)) or \
+                (np.diff(off) < 0).any() or mver.shape[0] != nmem:
+            raise ValueError("multicast_trees: mem_off is not the offsets of the members")
+        if weights is not None and np.asarray(weights).reshape(-1).shape[0] != ng:
+            raise ValueError("multicast_trees: one weight per group")
+        reached = np.zeros(nmem, np.uint8)
+        ent_off = np.zeros(ng + 1, np.int64)
+        none = np.zeros(0, np.int32) if entries else None
+        nrows = int(tree.shape[0])
+        self.last_multicast_ms = 0.0
+        if nmem == 0 or V == 0 or nrows == 0:
+            return reached, ent_off, none, (np.zeros(E, np.uint64) if loads else None)
+        tree = tree.contiguous()
+        d_root = t.from_numpy(root).to(self.dev)
+        d_off = t.from_numpy(off).to(self.dev)
+        d_row = t.from_numpy(mrow).to(self.dev)
+        d_ver = t.from_numpy(mver).to(self.dev)
+        d_w = None
+        if weights is not None and loads:
+            w = np.ascontiguousarray(np.asarray(weights, np.uint64).reshape(-1))
+            d_w = t.from_numpy(w.view(np.int64)).to(self.dev)
+        d_reach = t.zeros(nmem, dtype=t.uint8, device=self.dev)
+        d_cnt = t.zeros(ng, dtype=t.int64, device=self.dev)
+        d_load = t.zeros(max(E, 1), dtype=t.int64, device=self.dev) if loads else None
+        lay = {PORT16: _native.TREE_PORT16, SLOT: _native.TREE_SLOT,
+               INT32: _native.TREE_INT32}[layout]
+        self._ready()
+        self.ctx.multicast_trees_device(
+            tree.data_ptr(), lay, nrows, ng, d_root.data_ptr(), d_off.data_ptr(),
+            d_row.data_ptr(), d_ver.data_ptr(), d_w.data_ptr() if d_w is not None else 0,
+            d_reach.data_ptr(), d_cnt.data_ptr(), 0, 0,
+            d_load.data_ptr() if d_load is not None else 0, to_root=to_root, timing=True)
+        self.ctx.synchronize()              # raises if a row was not a tree
+        self.last_multicast_ms += self.ctx.last_kernel_ms()
+        d_eoff = t.zeros(ng + 1, dtype=t.int64, device=self.dev)
+        t.cumsum(d_cnt, 0, out=d_eoff[1:])
+        ent_off = d_eoff.cpu().numpy()
+        ent_edge = none
+        if entries and int(ent_off[-1]):
+            d_edge = t.empty(int(ent_off[-1]), dtype=t.int32, device=self.dev)
+            self._ready()
+            self.ctx.multicast_trees_device(
+                tree.data_ptr(), lay, nrows, ng, d_root.data_ptr(), d_off.data_ptr(),
+                d_row.data_ptr(), d_ver.data_ptr(), 0, 0, 0, d_eoff.data_ptr(),
+                d_edge.data_ptr(), 0, to_root=to_root, timing=True)
+            self.ctx.synchronize()
+            self.last_multicast_ms += self.ctx.last_kernel_ms()
+            ent_edge = d_edge.cpu().numpy()
+        load = d_load.cpu().numpy().view(np.uint64)[:E] if loads else None
+        return d_reach.cpu().numpy(), ent_off, ent_edge, load
 
     def fair_rates(self, export, tree, layout, rows, verts, mult=None, cap=None, extra=None,
                    to_root=False, timing=False):

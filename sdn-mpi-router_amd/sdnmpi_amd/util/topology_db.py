@@ -39,7 +39,7 @@ except Exception:   # noqa: BLE001 - Ryu is not a dependency of the engine
     OFPP_LOCAL = 0xfffe
 
 __all__ = ["TopologyDB", "LinkLoads", "SplitLinkLoads", "FailureLoads", "CostChangeLoads",
-           "CostTuning", "Admission", "FairRates", "OFPP_LOCAL",
+           "CostTuning", "Admission", "FairRates", "MulticastTree", "OFPP_LOCAL",
            "sdn_mpi_mac"]
 
 _INF = 0xFFFF
@@ -120,6 +120,39 @@ class SplitLinkLoads(LinkLoads):
         np.add.at(total, self._esrc, self.load)
         np.add.at(total, self._hsw, self.host_load.astype(np.float64))
         return self._dpids, total
+
+
+class MulticastTree(object):
+    """One group's multicast tree (:meth:`TopologyDB.multicast_tree`):
+    ``entries`` -- the sorted set of ``(dpid, out_port)`` tuples of the routes
+    from ``src`` to the members, each once --, ``unreached`` -- the member
+    MACs without a route (unknown hosts included), in the caller's order."""
+
+    def __init__(self, src, entries, unreached):
+        self.src = src
+        self.entries = entries
+        self.unreached = unreached
+
+    def as_dict(self):
+        """{dpid: (out_port, ...)}: the output actions of the one flow entry
+        each switch of the tree gets, ports ascending."""
+        out = {}
+        for d, p in self.entries:
+            out.setdefault(d, []).append(p)
+        return {d: tuple(ps) for d, ps in out.items()}
+
+
+class _EntryLoads(LinkLoads):
+    """:class:`LinkLoads` of multicast trees on a fabric that reuses a port
+    number on one switch: ``entry_loads`` holds the load of every ``(dpid,
+    out_port)`` entry, an entry that several links or last hops of a group
+    share counted once for that group; ``load`` and ``host_load`` stay per
+    link and per last hop."""
+
+    entry_loads = None
+
+    def as_dict(self):
+        return dict(self.entry_loads)
 
 
 class FailureLoads(object):
@@ -982,6 +1015,332 @@ class TopologyDB(object):
         with weight 1 -- the pairs of :meth:`mpi_flow_entries`."""
         pairs, weights = self._rank_pairs(rank_to_mac, traffic)
         return self.link_loads(pairs, weights, route)
+
+    # -- multicast trees ---------------------------------------------------
+    def _multicast_union(self, ex, rv, moff, mv, w, route, entries, loads):
+        """The multicast trees of switch-level groups: group g has root
+        ``rv[g]`` and the member switches ``mv[moff[g]:moff[g+1]]`` (dense
+        ids), weight ``w[g]``.  Returns ``(reached bool per member, ent_off,
+        ent_edge, load)`` as :meth:`RouteEngine.multicast_trees` does
+        (``ent_edge`` / ``load`` None when not asked for).  Rows come from the
+        caches in budget-sized chunks -- the roots' trees for the default
+        route, the members' next-hop rows for the shortest and least-cost
+        routes; when one chunk does not hold them all, the chunks' entries are
+        merged here (a group's members may lie in several chunks) and the
+        loads are counted from the merged entries."""
+        if route == "least_loaded":
+            raise ValueError("least-loaded routes are not prefix-consistent: the union of "
+                             "their entries is no tree")
+        if route not in ("default", "shortest", "least_cost"):
+            raise ValueError("route must be 'default', 'shortest' or 'least_cost'")
+        eng = self.engine
+        if not hasattr(eng, "multicast_trees"):
+            raise ValueError("the engine has no multicast_trees")
+        E, V = int(ex.csr.E), int(ex.csr.V)
+        ng, nmem = int(rv.shape[0]), int(mv.shape[0])
+        reached = np.zeros(nmem, bool)
+        if nmem == 0:
+            return (reached, np.zeros(ng + 1, np.int64), np.zeros(0, np.int32) if entries else None,
+                    np.zeros(E, np.uint64) if loads else None)
+        grp = np.repeat(np.arange(ng, dtype=np.int64), np.diff(moff))
+        c = self._cache
+        default = route == "default"
+        key = rv[grp] if default else mv               # the table row each member is walked in
+        want = np.unique(key).tolist()
+        batch = self._host_vertices(ex) if self._batch else ()
+        if route == "least_cost":
+            step = self._cost_cap(ex)
+        else:
+            store = c.dfs if default else c.sp
+            step = max(1, store.cap() - 1) if store.row_bytes else len(want)
+            if not default:    # the next-hop rows are widened to int32: bounded temporaries
+                step = min(step, max(1, TABLE_SLICE_ENTRIES // max(1, V)))
+        single = len(want) <= step
+
+        def slots_of(slot, verts):
+            """(the distinct table slots of the vertices, ascending; each vertex's index
+            among them) -- one dict lookup per distinct vertex"""
+            uv, inv = np.unique(verts, return_inverse=True)
+            sl = np.asarray([slot[v] for v in uv.tolist()], np.int64).reshape(-1)
+            us, pos = np.unique(sl, return_inverse=True)
+            return us, pos.reshape(-1)[inv.reshape(-1)]
+
+        found = []
+        for c0 in range(0, len(want), step):      # a budget's worth of rows at a time
+            chunk = want[c0:c0 + step]
+            sel = np.nonzero(np.isin(key, np.asarray(chunk, np.int64)))[0]
+            off = np.zeros(ng + 1, np.int64)
+            np.cumsum(np.bincount(grp[sel], minlength=ng), out=off[1:])
+            if route == "least_cost":
+                m = self._cost_rows(ex, chunk)
+                urows, rows = slots_of(m["slot"], key[sel])
+                tab, lay = _take(m["tabs"][1], urows), INT32
+            elif default:
+                tabs = c.dfs_rows(eng, chunk, batch if c0 == 0 else ())
+                urows, rows = slots_of(store.row, key[sel])
+                rows = urows[rows]
+                tab, lay = tabs[0], c.layout
+            else:
+                tabs = c.sp_rows(eng, chunk, batch if c0 == 0 else ())
+                urows, rows = slots_of(store.row, key[sel])
+                nh = _take(tabs[1], urows)
+                nh = _u16(nh) if V <= 0xFFFF else nh
+                tab = nh.astype(np.int32) if isinstance(nh, np.ndarray) else \
+                    nh.to(dtype=_torch().int32)
+                lay = INT32
+            r, eo, ee, ld = eng.multicast_trees(ex, tab, lay, rv, off, rows.reshape(-1), mv[sel],
+                                                w, to_root=not default,
+                                                entries=entries or not single,
+                                                loads=loads and single)
+            reached[sel] = np.asarray(r, bool)
+            if single:
+                return reached, eo, ee, ld
+            found.append(np.repeat(np.arange(ng, dtype=np.int64), np.diff(eo)) * max(E, 1) +
+                         np.asarray(ee, np.int64))
+        pairs = np.unique(np.concatenate(found))
+        pg, pe = pairs // max(E, 1), pairs % max(E, 1)
+        ent_off = np.zeros(ng + 1, np.int64)
+        np.cumsum(np.bincount(pg, minlength=ng), out=ent_off[1:])
+        load = None
+        if loads:
+            load = np.zeros(E, np.uint64)
+            np.add.at(load, pe, w[pg])
+        return reached, ent_off, pe.astype(np.int32) if entries else None, load
+
+    def _multicast_resolve(self, ex, groups):
+        """MAC groups -> switch groups.  Per member MAC that is known, is not
+        the group's source and whose source is known: its group ``mg``, its
+        position among the group's members ``mi``, its switch ``dv`` and last-
+        hop port ``last``; then the switch-level groups -- roots ``rv`` (-1:
+        unknown source), offsets ``moff`` and member switches ``mv``, unique
+        per group -- and ``inv``, the switch-level member of each MAC member."""
+        groups = [(a, list(ms)) for a, ms in groups]
+        ng = len(groups)
+        rv = np.full(ng, -1, np.int64)
+        # every distinct MAC is resolved once, to an id into ``info`` = (switch
+        # or -1 when unknown, last-hop port); the rest is array work
+        mid, info = {}, []
+
+        def ident(m):
+            if m not in mid:
+                ep = self._endpoint(m)
+                mid[m] = len(info)
+                info.append((-1, 0) if ep is None else
+                            (ex.index[ep[0]], self._last_hop(ep[0], ep[1], m)[1]))
+            return mid[m]
+
+        src = np.asarray([ident(a) for a, _ in groups], np.int64).reshape(-1)
+        ids = []
+        for _, ms in groups:
+            got = [mid.get(m, -1) for m in ms]
+            if -1 in got:                                  # (every MAC is checked)
+                got = [ident(m) for m in ms]
+            ids.append(np.asarray(got, np.int64).reshape(-1))
+        lens = np.asarray([x.shape[0] for x in ids], np.int64).reshape(-1)
+        ids = np.concatenate(ids) if ids else np.zeros(0, np.int64)
+        tab = np.asarray(info, np.int64).reshape(-1, 2)
+        if ng:
+            rv = tab[src, 0]
+        mg = np.repeat(np.arange(ng, dtype=np.int64), lens)
+        mi = np.arange(ids.shape[0], dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
+        keep = (tab[ids, 0] >= 0) & (ids != src[mg]) & (rv[mg] >= 0) if ids.size else \
+            np.zeros(0, bool)
+        mg, mi = mg[keep], mi[keep]
+        dv, last = tab[ids[keep], 0], tab[ids[keep], 1]
+        V = max(1, int(ex.csr.V))
+        skey, inv = np.unique(mg * V + dv, return_inverse=True)
+        moff = np.zeros(ng + 1, np.int64)
+        np.cumsum(np.bincount(skey // V, minlength=ng), out=moff[1:])
+        return groups, rv, mg, mi, dv, last, moff, skey % V, inv.reshape(-1)
+
+    def _multicast_entries(self, groups, route):
+        """(groups, off, dpid, port, got): the sorted entry set of every group
+        and ``got`` = (mg, mi) of the member MACs whose route exists."""
+        ex = self.graph()
+        groups, rv, mg, mi, dv, last, moff, mv, inv = self._multicast_resolve(ex, groups)
+        ng = len(groups)
+        w = np.ones(ng, np.uint64)
+        reach, eo, ee, _ = self._multicast_union(ex, rv, moff, mv, w, route, True, False)
+        ok = reach[inv] if inv.size else np.zeros(0, bool)
+        csr = ex.csr
+        rp = np.asarray(csr.row_ptr, np.int64)
+        esrc = np.repeat(np.arange(csr.V, dtype=np.int64), np.diff(rp))
+        ee = np.asarray(ee, np.int64)
+        eg = np.repeat(np.arange(ng, dtype=np.int64), np.diff(eo))
+        dp = np.asarray(csr.dpids, np.int64)
+        V = max(1, int(csr.V))
+        eport = np.asarray(csr.port, np.int64)[ee]
+        if ng * V < (1 << 31) and (eport.size == 0 or 0 <= eport.min()) and \
+                (not ok.any() or 0 <= last[ok].min()) and \
+                max(int(eport.max()) if eport.size else 0, int(last.max()) if last.size else 0) \
+                < (1 << 32):
+            # one int64 key per entry -- (group, dense switch, port), the order of (group,
+            # dpid, port) since dense ids ascend with the dpids --, each entry once
+            key = np.unique(np.concatenate([((eg * V + esrc[ee]) << 32) | eport,
+                                            ((mg[ok] * V + dv[ok]) << 32) | last[ok]]))
+            gs, pt = key >> 32, key & 0xFFFFFFFF
+            g_of, sw = gs // V, dp[gs % V]
+        else:
+            rec = np.unique(np.concatenate([np.stack([eg, esrc[ee], eport], 1),
+                                            np.stack([mg[ok], dv[ok], last[ok]], 1)]
+                                           ).reshape(-1, 3), axis=0)
+            g_of, sw, pt = rec[:, 0], dp[rec[:, 1]], rec[:, 2]
+        off = np.zeros(ng + 1, np.int64)
+        np.cumsum(np.bincount(g_of, minlength=ng), out=off[1:])
+        return groups, off, sw.astype(np.asarray(csr.dpids).dtype), pt.astype(np.int32), \
+            (mg[ok], mi[ok])
+
+    def multicast_trees(self, groups, route="default"):
+        """The flow entries of one-to-many groups with in-network replication:
+        ``groups = [(src_mac, [dst_mac, ...]), ...]``; group i's multicast tree
+        is installed as one entry per (switch, out port) -- OpenFlow 1.0 lets
+        an entry carry several output actions, so a switch on several members'
+        routes forwards the frame once per distinct port.
+
+        Returns ``(off, dpid, port)`` numpy arrays shaped as
+        :meth:`route_entries` returns them.  Defining property: group i's
+        slice ``zip(dpid[off[i]:off[i+1]], port[off[i]:off[i+1]])`` equals
+        ``sorted(set(e for m in members for e in route(src, m)))`` where
+        ``route`` is ``find_route(src, m)`` (``"default"``),
+        ``find_route(src, m, multiple=True)[0]`` (``"shortest"``) or
+        ``find_route_least_cost(src, m)`` (``"least_cost"``).  Unknown hosts,
+        unreachable members and ``m == src`` drop out.  The shortest and
+        least-cost routes are the lexicographically smallest ones, so they are
+        prefix-consistent and the union is a tree, like the default route's;
+        ``"least_loaded"`` raises ValueError (its routes are not), and so does
+        an engine without ``multicast_trees``.  No per-member route is built:
+        the GPU marks the links of all members' walks in one bit map per group
+        (multicast.hip) and only the union comes back; the last hops -- the
+        member's host port or OFPP_LOCAL -- are added here."""
+        _, off, dpid, port, _ = self._multicast_entries(groups, route)
+        return off, dpid, port
+
+    def multicast_tree(self, src_mac, dst_macs, route="default"):
+        """:meth:`multicast_trees` of one group, as a :class:`MulticastTree`."""
+        dst_macs = list(dst_macs)
+        _, off, dpid, port, (_, mi) = self._multicast_entries([(src_mac, dst_macs)], route)
+        have = set(mi.tolist())
+        unreached = [m for i, m in enumerate(dst_macs) if i not in have and m != src_mac]
+        return MulticastTree(src_mac, list(zip(dpid.tolist(), port.tolist())), unreached)
+
+    def multicast_link_loads(self, groups, weights=None, route="default"):
+        """What the links carry when every group's source sends ``weights[g]``
+        (non-negative ints, e.g. bytes; None: 1 each) to its members down its
+        multicast tree (:meth:`multicast_trees`): every link and every
+        last-hop port of group g's tree carries ``weights[g]`` ONCE, however
+        many members lie behind it -- as a :class:`LinkLoads`.  Its counterpart
+        for the unicast fan-out, where the source sends one copy per member, is
+        :meth:`link_loads` over the (src, member) pairs with the group's weight
+        on each; the peak of the two is what in-network replication saves.
+        Unknown hosts, unreachable members and ``m == src`` contribute nothing;
+        ``route`` as in :meth:`multicast_trees`.  The loads are summed on the
+        GPU from the groups' bit maps (no entry is built); sums are unsigned
+        64-bit and wrap."""
+        ex = self.graph()
+        groups, rv, mg, mi, dv, last, moff, mv, inv = self._multicast_resolve(ex, groups)
+        w = _weights(weights, len(groups))
+        csr = ex.csr
+        esrc = np.repeat(np.arange(csr.V, dtype=np.int64),
+                         np.diff(np.asarray(csr.row_ptr, np.int64)))
+        port = np.asarray(csr.port, np.int64)
+        # a fabric that reuses a port number on one switch (two links, or a
+        # link and a host: the random fixtures do) has entries that several
+        # links or last hops share; an entry is one output action, so as_dict
+        # counts it once per group, from the entries themselves
+        lkey = (esrc << 32) | (port & 0xFFFFFFFF)
+        reuse = np.unique(lkey).size != lkey.size or \
+            bool(np.isin((dv << 32) | (last & 0xFFFFFFFF), lkey).any())
+        reach, eo, ee, load = self._multicast_union(ex, rv, moff, mv, w, route, reuse, True)
+        ok = reach[inv] if inv.size else np.zeros(0, bool)
+        # the last hops: each (group, switch, port) once
+        V = max(1, int(csr.V))
+        lo = last[ok]
+        if len(groups) * V < (1 << 31) and (lo.size == 0 or (0 <= lo.min() and
+                                                             lo.max() < (1 << 32))):
+            k = np.unique(((mg[ok] * V + dv[ok]) << 32) | lo)       # one int64 key per last hop
+            rec = np.stack([(k >> 32) // V, (k >> 32) % V, k & 0xFFFFFFFF], 1)
+        else:
+            rec = np.unique(np.stack([mg[ok], dv[ok], lo], 1).reshape(-1, 3), axis=0)
+        if rec.shape[0] and 0 <= rec[:, 2].min() and rec[:, 2].max() < (1 << 32):
+            hk, hinv = np.unique((rec[:, 1] << 32) | rec[:, 2], return_inverse=True)
+            hkey = np.stack([hk >> 32, hk & 0xFFFFFFFF], 1)
+        else:
+            hkey, hinv = np.unique(rec[:, 1:], axis=0, return_inverse=True)
+        hload = np.zeros(hkey.shape[0], np.uint64)
+        np.add.at(hload, hinv.reshape(-1), w[rec[:, 0]])
+        if not reuse:
+            return self._link_loads_result(ex, load, hkey.reshape(-1, 2), hload)
+        out = self._link_loads_result(ex, load, hkey.reshape(-1, 2), hload, _EntryLoads)
+        ee = np.asarray(ee, np.int64)
+        eg = np.repeat(np.arange(len(groups), dtype=np.int64), np.diff(eo))
+        ent = np.unique(np.concatenate([np.stack([eg, esrc[ee], port[ee]], 1), rec]).reshape(-1, 3),
+                        axis=0)
+        dp = np.asarray(csr.dpids, np.int64)
+        sums = {}
+        for g, d, p in zip(ent[:, 0].tolist(), dp[ent[:, 1]].tolist(), ent[:, 2].tolist()):
+            sums[(d, p)] = (sums.get((d, p), 0) + int(w[g])) & _U64
+        out.entry_loads = {k: x for k, x in sums.items() if x}
+        return out
+
+    def mpi_bcast_entries(self, rank_to_mac, roots=None, route="default"):
+        """The flow entries of MPI broadcasts with in-network replication: for
+        every root rank of ``roots`` (default: every rank of ``rank_to_mac``)
+        the multicast tree from its host to the hosts of all other ranks,
+        grouped by switch as :meth:`switch_fdb_entries` lays entries out.
+
+        Returns ``(dpids, off, root_rank, out_port, dst_rank)``: switch
+        ``dpids[k]`` holds the entries ``off[k]:off[k+1]``; an entry forwards
+        root ``root_rank[j]``'s broadcast out of ``out_port[j]``.  On a
+        delivering entry -- a member's host port or OFPP_LOCAL, where the
+        router would add SetDlDst (reference ``router.py:97-100``) --
+        ``dst_rank[j]`` is the member rank, one entry per member rank (two
+        ranks of one host give two); on a transit entry it is -1.  Switches
+        ascend by dpid; within a switch the entries ascend by root rank, the
+        transit entries (by port) before the delivering ones (by member rank).
+        A rank whose MAC is the root's own, an unknown MAC and an unreachable
+        host get no entry."""
+        ranks = sorted(rank_to_mac)
+        roots = ranks if roots is None else [r for r in roots if r in rank_to_mac]
+        members = [[b for b in ranks if b != a] for a in roots]
+        groups = [(rank_to_mac[a], [rank_to_mac[b] for b in ms]) for a, ms in zip(roots, members)]
+        ex = self.graph()
+        groups, rv, mg, mi, dv, last, moff, mv, inv = self._multicast_resolve(ex, groups)
+        ng = len(groups)
+        reach, eo, ee, _ = self._multicast_union(ex, rv, moff, mv, np.ones(ng, np.uint64), route,
+                                                 True, False)
+        ok = reach[inv] if inv.size else np.zeros(0, bool)
+        csr = ex.csr
+        esrc = np.repeat(np.arange(csr.V, dtype=np.int64), np.diff(np.asarray(csr.row_ptr, np.int64)))
+        ee = np.asarray(ee, np.int64)
+        eg = np.repeat(np.arange(ng, dtype=np.int64), np.diff(eo))
+        root_r = np.asarray(roots, np.int64).reshape(-1)
+        mrank = np.asarray([members[g][i] for g, i in zip(mg[ok].tolist(), mi[ok].tolist())],
+                           np.int64)
+        sw = np.concatenate([esrc[ee], dv[ok]])
+        rr = np.concatenate([root_r[eg], root_r[mg[ok]]]) if ng else np.zeros(0, np.int64)
+        pt = np.concatenate([np.asarray(csr.port, np.int64)[ee], last[ok]])
+        dr = np.concatenate([np.full(ee.shape[0], -1, np.int64), mrank])
+        order = np.lexsort((pt, dr, dr >= 0, rr, sw))
+        sw, rr, pt, dr = sw[order], rr[order], pt[order], dr[order]
+        cnt = np.bincount(sw, minlength=int(csr.V)) if sw.size else np.zeros(int(csr.V), np.int64)
+        has = np.nonzero(cnt)[0]
+        off = np.zeros(has.shape[0] + 1, np.int64)
+        np.cumsum(cnt[has], out=off[1:])
+        return np.asarray(csr.dpids, np.int64)[has], off, rr, pt.astype(np.int32), dr
+
+    def mpi_bcast_link_loads(self, rank_to_mac, traffic=None, route="default"):
+        """:meth:`multicast_link_loads` of an MPI job's broadcasts: ``traffic``
+        = {root_rank: bytes} (a rank the map lacks is skipped); None: every
+        rank broadcasts 1 -- MPI_Allgather as broadcasts.  Each root's group
+        is the hosts of all other ranks."""
+        ranks = sorted(rank_to_mac)
+        if traffic is None:
+            roots, weights = ranks, None
+        else:
+            roots = [r for r in traffic if r in rank_to_mac]
+            weights = [traffic[r] for r in roots]
+        groups = [(rank_to_mac[a], [rank_to_mac[b] for b in ranks if b != a]) for a in roots]
+        return self.multicast_link_loads(groups, weights, route)
 
     # -- predicted link loads under ECMP ----------------------------------
     def _switch_pair_ecmp_loads(self, ex, sv, dv, w, split):
