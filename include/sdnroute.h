@@ -880,6 +880,17 @@ int sdnr_last_kernel_ms(sdnr_ctx *ctx, float *ms);
  * shortest kernel, 1 for single-launch kernels (0 before the first call). */
 int sdnr_last_launches(const sdnr_ctx *ctx, int32_t *launches);
 
+/* Number of workgroups in the last launch of a row-persistent kernel: the
+ * kernels of sdnr_link_loads, sdnr_ecmp_link_loads, sdnr_cost_ecmp_link_loads,
+ * sdnr_cost_tables, sdnr_widest_tables, sdnr_failure_ecmp_link_loads,
+ * sdnr_whatif_ecmp_link_loads, sdnr_lfa_tables, sdnr_fair_rates,
+ * sdnr_ecmp_fair_rates (their row kernel), sdnr_multicast_trees and
+ * sdnr_ecmp_counts give every workgroup the rows (batches, items, groups) r,
+ * r + grid, r + 2 * grid, ...: with more units of work than this a workgroup
+ * takes more than one.  The other entry points leave it as it was (0 before
+ * the first such call). */
+int sdnr_last_grid(const sdnr_ctx *ctx, int64_t *workgroups);
+
 /* Sources the last sdnr_dfs_tables* call searched (waits for that call): the
  * batch size, or, when the call folded twin classes, one per class present
  * in the batch -- the other rows were derived (0 before the first call). */

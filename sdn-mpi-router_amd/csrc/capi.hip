@@ -2168,6 +2168,14 @@ int sdnr_last_launches(const sdnr_ctx *ctx, int32_t *launches)
     return SDNR_OK;
 }
 
+int sdnr_last_grid(const sdnr_ctx *ctx, int64_t *workgroups)
+{
+    CHECK_CTX(ctx);
+    if (!workgroups) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_last_grid: null out");
+    *workgroups = ctx->last_grid;
+    return SDNR_OK;
+}
+
 int sdnr_last_kernel_ms(sdnr_ctx *ctx, float *ms)
 {
     CHECK_CTX(ctx);

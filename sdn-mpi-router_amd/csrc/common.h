@@ -224,6 +224,7 @@ struct sdnr_ctx {
     bool timed = false;
     const char *last_kernel = "";       // variant launched by the last table call
     int32_t last_launches = 0;          // main-kernel launches of the last table call
+    int64_t last_grid = 0;              // workgroups of the last row-persistent launch (sdnr_last_grid)
     int32_t last_sweeps = 0;            // Bellman-Ford sweeps of the last APSP call
     int32_t plane_depth = 0;            // levels the bit-plane BFS last needed on this graph
     int *d_err = nullptr;               // kernel watchdog word (0 = ok)

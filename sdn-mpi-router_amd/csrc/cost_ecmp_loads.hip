@@ -247,6 +247,7 @@ int sdnr_launch_cost_ecmp_link_loads(sdnr_ctx *ctx, const uint32_t *d_pcost, int
         int64_t g = (int64_t)ctx->num_cus * per_cu;
         if (g > nrows) g = nrows;
         ctx->last_kernel = "cost_ecmp_loads_kernel<lds>";
+        ctx->last_grid = g;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kCostEcmpThreads), lds, ctx->stream, V,
                            nrows, hop ? 1 : 0, ctx->row_ptr, ctx->col, ctx->cost, d_pcost,
@@ -262,6 +263,7 @@ int sdnr_launch_cost_ecmp_link_loads(sdnr_ctx *ctx, const uint32_t *d_pcost, int
         const int rc = sdnr_reserve(&ctx->scratch, &ctx->scratch_bytes, stride * (size_t)g);
         if (rc) return rc;
         ctx->last_kernel = "cost_ecmp_loads_kernel<global>";
+        ctx->last_grid = g;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL(cost_ecmp_loads_kernel<false>, dim3((unsigned)g),
                            dim3(kCostEcmpThreads), 0, ctx->stream, V, nrows, hop ? 1 : 0,

@@ -208,6 +208,7 @@ static int launch_lds(sdnr_ctx *ctx, const char *name, const int32_t *d_dst, int
     int64_t g = (int64_t)ctx->num_cus * per_cu;
     if (g > nbatch) g = nbatch;
     ctx->last_kernel = name;
+    ctx->last_grid = g;
     if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kCostThreads), lds, ctx->stream, V, ndst,
                        ctx->row_ptr, ctx->col, ctx->port, ctx->cost, d_dst, d_pcost, d_nh,
@@ -240,6 +241,7 @@ int sdnr_launch_cost_tables(sdnr_ctx *ctx, const int32_t *d_dst, int32_t ndst, u
         if (g > fit) g = fit < 1 ? 1 : fit;
         if ((rc = sdnr_reserve(&ctx->scratch, &ctx->scratch_bytes, stride * (size_t)g))) return rc;
         ctx->last_kernel = "cost_tables_kernel<global,4>";
+        ctx->last_grid = g;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL((cost_tables_kernel<false, B>), dim3((unsigned)g), dim3(kCostThreads),
                            0, ctx->stream, V, ndst, ctx->row_ptr, ctx->col, ctx->port, ctx->cost,

@@ -280,6 +280,7 @@ int sdnr_launch_ecmp_counts(sdnr_ctx *ctx, const uint16_t *d_dist, int32_t ndst,
         auto k = stage ? ecmp_count_rows_kernel<NW, true> : ecmp_count_rows_kernel<NW, false>;
         sdnr_allow_lds(reinterpret_cast<const void *>(k), wlds);
         ctx->last_kernel = stage ? "ecmp_count_rows_kernel<stage>" : "ecmp_count_rows_kernel";
+        ctx->last_grid = grid;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL(k, dim3(grid), dim3(NW * 64), wlds, ctx->stream, V, ndst, ctx->adj16,
                            ctx->deg32, d_dist, d_paths);
@@ -293,6 +294,7 @@ int sdnr_launch_ecmp_counts(sdnr_ctx *ctx, const uint16_t *d_dist, int32_t ndst,
         int grid = ctx->num_cus * 4;
         if (grid > ndst) grid = ndst;
         ctx->last_kernel = "ecmp_count_global_kernel";
+        ctx->last_grid = grid;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL(ecmp_count_global_kernel, dim3(grid), dim3(1024), 0, ctx->stream, V,
                            ndst, ctx->row_ptr, ctx->col, d_dist, d_paths);
@@ -304,6 +306,7 @@ int sdnr_launch_ecmp_counts(sdnr_ctx *ctx, const uint16_t *d_dist, int32_t ndst,
     if (grid > ndst) grid = ndst;
     sdnr_allow_lds(reinterpret_cast<const void *>(ecmp_count_kernel), lds);
     ctx->last_kernel = "ecmp_count_kernel";
+    ctx->last_grid = grid;
     if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     hipLaunchKernelGGL(ecmp_count_kernel, dim3(grid), dim3(1024), lds, ctx->stream, V, ndst,
                        ctx->row_ptr, ctx->col, d_dist, d_paths);

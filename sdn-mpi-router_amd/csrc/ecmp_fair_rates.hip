@@ -522,6 +522,7 @@ int sdnr_launch_ecmp_fair_rates(sdnr_ctx *ctx, const uint32_t *d_pcost, int32_t 
     auto fn_lds = ecmp_fair_rows_kernel<true>;
     if (lds_form) sdnr_allow_lds(reinterpret_cast<const void *>(fn_lds), lds);
     ctx->last_kernel = lds_form ? "ecmp_fair_rows_kernel<lds>" : "ecmp_fair_rows_kernel<global>";
+    ctx->last_grid = g;
 
     int k = 0, done = -1;
     while (done < 0) {

@@ -167,6 +167,7 @@ int sdnr_launch_ecmp_link_loads(sdnr_ctx *ctx, const uint16_t *d_dist, int32_t n
         int64_t g = (int64_t)ctx->num_cus * per_cu;
         if (g > nrows) g = nrows;
         ctx->last_kernel = "ecmp_loads_kernel<lds>";
+        ctx->last_grid = g;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kEcmpLoadsThreads), lds, ctx->stream, V,
                            nrows, hop ? 1 : 0, ctx->row_ptr, ctx->col, d_dist, d_pair_off, pair_lo,
@@ -182,6 +183,7 @@ int sdnr_launch_ecmp_link_loads(sdnr_ctx *ctx, const uint16_t *d_dist, int32_t n
         const int rc = sdnr_reserve(&ctx->scratch, &ctx->scratch_bytes, stride * (size_t)g);
         if (rc) return rc;
         ctx->last_kernel = "ecmp_loads_kernel<global>";
+        ctx->last_grid = g;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL(ecmp_loads_kernel<false>, dim3((unsigned)g), dim3(kEcmpLoadsThreads),
                            16, ctx->stream, V, nrows, hop ? 1 : 0, ctx->row_ptr, ctx->col, d_dist,

@@ -521,6 +521,7 @@ int sdnr_launch_fair_rates(sdnr_ctx *ctx, const void *d_tree, int32_t layout, bo
     auto fn_lds = fair_rows_kernel<uint16_t, true>;
     if (lds_form) sdnr_allow_lds(reinterpret_cast<const void *>(fn_lds), lds);
     ctx->last_kernel = lds_form ? "fair_rows_kernel<lds>" : "fair_rows_kernel<global>";
+    ctx->last_grid = g;
 
     int k = 0, done = -1;
     while (done < 0) {

@@ -285,6 +285,7 @@ int launch_main(sdnr_ctx *ctx, const char *name, const uint32_t *cost, const uin
     if (g > ndst) g = ndst;
     ctx->last_kernel = name;
     ctx->last_launches = 1;
+    ctx->last_grid = g;
     if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kLfaThreads), lds, ctx->stream, V, ndst,
                        ctx->row_ptr, ctx->col, ctx->port, cost, d_pall, back, nn, off, d_dst,

@@ -172,6 +172,7 @@ int sdnr_launch_link_loads(sdnr_ctx *ctx, const void *d_tree, int32_t layout, bo
         int64_t g = (int64_t)ctx->num_cus * per_cu;
         if (g > nrows) g = nrows;
         ctx->last_kernel = "link_loads_kernel<lds>";
+        ctx->last_grid = g;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kLoadsThreads), lds, ctx->stream, t, V,
                            ctx->E, nrows, max_rounds, ctx->row_ptr, ctx->col, d_pair_off, pair_lo,
@@ -187,6 +188,7 @@ int sdnr_launch_link_loads(sdnr_ctx *ctx, const void *d_tree, int32_t layout, bo
         const int rc = sdnr_reserve(&ctx->scratch, &ctx->scratch_bytes, stride * (size_t)g);
         if (rc) return rc;
         ctx->last_kernel = "link_loads_kernel<global>";
+        ctx->last_grid = g;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL((link_loads_kernel<uint32_t, false>), dim3((unsigned)g),
                            dim3(kLoadsThreads), 0, ctx->stream, t, V, ctx->E, nrows, max_rounds,

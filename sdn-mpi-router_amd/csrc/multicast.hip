@@ -275,6 +275,7 @@ int sdnr_launch_multicast_trees(sdnr_ctx *ctx, const void *d_tree, int32_t layou
         int64_t g = (int64_t)ctx->num_cus * 4;             // 4 x 32 KiB of the CU's LDS
         if (g > ngroups) g = ngroups;
         ctx->last_kernel = "multicast_trees_kernel<lds>";
+        ctx->last_grid = g;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kMcastThreads), lds, ctx->stream, t, V, E,
                            nrows, ngroups, ctx->row_ptr, ctx->col, d_root, d_mem_off, mem_lo,
@@ -290,6 +291,7 @@ int sdnr_launch_multicast_trees(sdnr_ctx *ctx, const void *d_tree, int32_t layou
         const int rc = sdnr_reserve(&ctx->scratch, &ctx->scratch_bytes, stride * (size_t)g);
         if (rc) return rc;
         ctx->last_kernel = "multicast_trees_kernel<global>";
+        ctx->last_grid = g;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL((multicast_trees_kernel<false>), dim3((unsigned)g), dim3(kMcastThreads),
                            0, ctx->stream, t, V, E, nrows, ngroups, ctx->row_ptr, ctx->col, d_root,

@@ -437,6 +437,7 @@ int sdnr_launch_whatif_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *d_dst, int3
         int64_t g = (int64_t)ctx->num_cus * per_cu;
         if (g > nitems) g = nitems;
         ctx->last_kernel = "whatif_ecmp_loads_kernel<lds>";
+        ctx->last_grid = g;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kWhatifThreads), lds, ctx->stream, V,
                            ctx->E, nrows, nscen, hop ? 1 : 0, ctx->row_ptr, ctx->col, cost, d_dst,
@@ -453,6 +454,7 @@ int sdnr_launch_whatif_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *d_dst, int3
         const int rc = sdnr_reserve(&ctx->scratch, &ctx->scratch_bytes, stride * (size_t)g);
         if (rc) return rc;
         ctx->last_kernel = "whatif_ecmp_loads_kernel<global>";
+        ctx->last_grid = g;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         hipLaunchKernelGGL(whatif_ecmp_loads_kernel<false>, dim3((unsigned)g),
                            dim3(kWhatifThreads), 0, ctx->stream, V, ctx->E, nrows, nscen,

@@ -280,6 +280,7 @@ int launch_lds(sdnr_ctx *ctx, const char *name, const uint32_t *cost, const uint
     int64_t g = (int64_t)ctx->num_cus * per_cu;
     if (g > nbatch) g = nbatch;
     ctx->last_kernel = name;
+    ctx->last_grid = g;
     if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kWidestThreads), lds, ctx->stream, V, ndst,
                        ctx->row_ptr, ctx->col, ctx->port, cost, d_util, d_pcost, d_dst, d_bott,
@@ -329,6 +330,7 @@ int sdnr_launch_widest_tables(sdnr_ctx *ctx, const uint32_t *d_pcost, const uint
         if (g > fit) g = fit < 1 ? 1 : fit;
         if ((rc = sdnr_reserve(&ctx->scratch, &ctx->scratch_bytes, stride * (size_t)g))) return rc;
         ctx->last_kernel = "widest_tables_kernel<global,4>";
+        ctx->last_grid = g;
         if (ctx->timed) SDNR_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         auto fn = cost ? widest_tables_kernel<false, B, true> : widest_tables_kernel<false, B, false>;
         hipLaunchKernelGGL(fn, dim3((unsigned)g), dim3(kWidestThreads), 0, ctx->stream, V, ndst,

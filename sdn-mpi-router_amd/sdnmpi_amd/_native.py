@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_last_dfs_form", "sdnr_last_dfs_quotient",
     "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables", "sdnr_whatif_ecmp_link_loads",
     "sdnr_widest_tables", "sdnr_fair_rates", "sdnr_ecmp_fair_rates", "sdnr_multicast_trees",
+    "sdnr_last_grid",
 )
 
 
@@ -106,6 +107,7 @@ def _bind(L):
         "sdnr_last_kernel_ms": ([vp, ctypes.POINTER(ctypes.c_float)], c_int),
         "sdnr_last_kernel": ([vp], ctypes.c_char_p),
         "sdnr_last_launches": ([vp, ctypes.POINTER(i32)], c_int),
+        "sdnr_last_grid": ([vp, ctypes.POINTER(ctypes.c_int64)], c_int),
         "sdnr_last_sweeps": ([vp, ctypes.POINTER(i32)], c_int),
         "sdnr_edge_ports": ([vp, vp, i32, vp, i32, vp, u32], c_int),
         "sdnr_dfs_rows_affected": ([vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, u32], c_int),
@@ -742,6 +744,14 @@ class Context(object):
     def last_launches(self):
         n = ctypes.c_int32()
         _check(self._lib.sdnr_last_launches(self._h, ctypes.byref(n)))
+        return n.value
+
+    def last_grid(self):
+        """Workgroups of the last row-persistent launch (sdnr_last_grid): with
+        more rows, batches, items or groups than this a workgroup took more
+        than one."""
+        n = ctypes.c_int64()
+        _check(self._lib.sdnr_last_grid(self._h, ctypes.byref(n)))
         return n.value
 
     def twin_reps(self):
