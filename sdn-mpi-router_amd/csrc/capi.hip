@@ -1385,49 +1385,8 @@ int sdnr_dfs_rows_affected(sdnr_ctx *ctx, const uint32_t *tree, const void *dept
                                          links, nremoved, nadded, affected);
 }
 
-int sdnr_link_loads(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nrows,
-                    const int64_t *pair_off, const int32_t *dsts, const uint64_t *weight,
-                    uint64_t *load, uint32_t flags)
-{
-    CHECK_CTX(ctx);
-    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_link_loads: no graph uploaded");
-    if (!(flags & SDNR_DEVICE_PTRS))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: device pointers only");
-    if (nrows < 0) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: negative count");
-    if (layout != SDNR_TREE_INT32 && layout != SDNR_TREE_PORT16 && layout != SDNR_TREE_SLOT)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: layout %d", layout);
-    const bool to_root = (flags & SDNR_LOADS_TO_ROOT) != 0;
-    if (to_root && layout != SDNR_TREE_INT32)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: SDNR_LOADS_TO_ROOT takes int32 "
-                         "next-hop rows (layout %d)", layout);
-    if (layout == SDNR_TREE_PORT16 && ctx->V > 0xFFFF)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: port16 needs V <= 65535 (V=%d)",
-                         ctx->V);
-    if (layout == SDNR_TREE_SLOT && ctx->V > (1 << 26) - 1)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: slots need V < 2^26 (V=%d)", ctx->V);
-    if (nrows == 0) return SDNR_OK;
-    if (!tree || !pair_off || !load)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: null pointer");
-    SDNR_HIP(hipSetDevice(ctx->device));
-    // the bounds of the pair list: pair_off[0], pair_off[nrows] (two int64)
-    int w[4];
-    int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off), 2, w);
-    if (!rc) rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off + nrows), 2, w + 2);
-    if (rc) return rc;
-    const int64_t lo = (int64_t)(((uint64_t)(uint32_t)w[1] << 32) | (uint32_t)w[0]);
-    const int64_t hi = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
-    if (lo < 0 || hi < lo)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: pair_off not monotone (pair_off[0]="
-                         "%lld, pair_off[%d]=%lld)", (long long)lo, nrows, (long long)hi);
-    if (hi == lo || ctx->V == 0) return SDNR_OK;
-    if (!dsts) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_link_loads: null pointer");
-    ctx->timed = (flags & SDNR_TIMING) != 0;
-    return sdnr_launch_link_loads(ctx, tree, layout, to_root, nrows, pair_off, lo, hi, dsts,
-                                  weight, load);
-}
-
-// off[0] and off[n] of a device int64 offset array (two int64 read back)
-static int fetch_offset_ends(sdnr_ctx *ctx, const int64_t *off, int32_t n, int64_t *lo, int64_t *hi)
+// off[0] and off[n] of a device int64 offset list (two int64 read back)
+static int fetch_bounds(sdnr_ctx *ctx, const int64_t *off, int32_t n, int64_t *lo, int64_t *hi)
 {
     int w[4];
     int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(off), 2, w);
@@ -1438,6 +1397,73 @@ static int fetch_offset_ends(sdnr_ctx *ctx, const int64_t *off, int32_t n, int64
     return SDNR_OK;
 }
 
+// The prologue of the pair-list calls (link, multicast, fair, ecmp-fair, ecmp,
+// cost-ecmp, failure and what-if loads) in two steps, because each call has
+// checks of its own between them and the order of the messages is part of the
+// interface.  Step 1, the opening: a graph is uploaded, the pointers are device
+// pointers, no count is negative.
+static int open_pair_call(const sdnr_ctx *ctx, uint32_t flags, bool negative, const char *name)
+{
+    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "%s: no graph uploaded", name);
+    if (!(flags & SDNR_DEVICE_PTRS))
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: device pointers only", name);
+    if (negative) return sdnr_fail(SDNR_ERR_INVAL, "%s: negative count", name);
+    return SDNR_OK;
+}
+
+// Step 2, per offset list: its bounds off[0] <= off[n] read back, and whether
+// the list is empty -- nothing to do, which is no error and the caller's to act on
+static int list_bounds(sdnr_ctx *ctx, const int64_t *off, int32_t n, const char *name,
+                       const char *what, int64_t *lo, int64_t *hi, bool *empty = nullptr)
+{
+    const int rc = fetch_bounds(ctx, off, n, lo, hi);
+    if (rc) return rc;
+    if (*lo < 0 || *hi < *lo)
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: %s not monotone (%s[0]=%lld, %s[%d]=%lld)", name,
+                         what, what, (long long)*lo, what, n, (long long)*hi);
+    if (empty) *empty = *hi == *lo;
+    return SDNR_OK;
+}
+
+// A tree table's layout against the graph: flag_name is the call's to-root flag
+static int check_tree_layout(const sdnr_ctx *ctx, int32_t layout, bool to_root, const char *name,
+                             const char *flag_name)
+{
+    if (layout != SDNR_TREE_INT32 && layout != SDNR_TREE_PORT16 && layout != SDNR_TREE_SLOT)
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: layout %d", name, layout);
+    if (to_root && layout != SDNR_TREE_INT32)
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: %s takes int32 next-hop rows (layout %d)", name,
+                         flag_name, layout);
+    if (layout == SDNR_TREE_PORT16 && ctx->V > 0xFFFF)
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: port16 needs V <= 65535 (V=%d)", name, ctx->V);
+    if (layout == SDNR_TREE_SLOT && ctx->V > (1 << 26) - 1)
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: slots need V < 2^26 (V=%d)", name, ctx->V);
+    return SDNR_OK;
+}
+
+int sdnr_link_loads(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nrows,
+                    const int64_t *pair_off, const int32_t *dsts, const uint64_t *weight,
+                    uint64_t *load, uint32_t flags)
+{
+    static const char name[] = "sdnr_link_loads";
+    CHECK_CTX(ctx);
+    int rc = open_pair_call(ctx, flags, nrows < 0, name);
+    if (rc) return rc;
+    const bool to_root = (flags & SDNR_LOADS_TO_ROOT) != 0;
+    if ((rc = check_tree_layout(ctx, layout, to_root, name, "SDNR_LOADS_TO_ROOT"))) return rc;
+    if (nrows == 0) return SDNR_OK;
+    if (!tree || !pair_off || !load) return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
+    SDNR_HIP(hipSetDevice(ctx->device));
+    int64_t lo, hi;
+    bool empty;
+    if ((rc = list_bounds(ctx, pair_off, nrows, name, "pair_off", &lo, &hi, &empty))) return rc;
+    if (empty || ctx->V == 0) return SDNR_OK;
+    if (!dsts) return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
+    ctx->timed = (flags & SDNR_TIMING) != 0;
+    return sdnr_launch_link_loads(ctx, tree, layout, to_root, nrows, pair_off, lo, hi, dsts,
+                                  weight, load);
+}
+
 int sdnr_multicast_trees(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nrows,
                          int32_t ngroups, const int32_t *root, const int64_t *mem_off,
                          const int32_t *mem_row, const int32_t *mem_vertex,
@@ -1445,45 +1471,25 @@ int sdnr_multicast_trees(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_
                          const int64_t *ent_off, int32_t *ent_edge, uint64_t *load,
                          uint32_t flags)
 {
+    static const char name[] = "sdnr_multicast_trees";
     CHECK_CTX(ctx);
-    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_multicast_trees: no graph uploaded");
-    if (!(flags & SDNR_DEVICE_PTRS))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: device pointers only");
-    if (nrows < 0 || ngroups < 0)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: negative count");
-    if (layout != SDNR_TREE_INT32 && layout != SDNR_TREE_PORT16 && layout != SDNR_TREE_SLOT)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: layout %d", layout);
+    int rc = open_pair_call(ctx, flags, nrows < 0 || ngroups < 0, name);
+    if (rc) return rc;
     const bool to_root = (flags & SDNR_MCAST_TO_ROOT) != 0;
-    if (to_root && layout != SDNR_TREE_INT32)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: SDNR_MCAST_TO_ROOT takes int32 "
-                         "next-hop rows (layout %d)", layout);
-    if (layout == SDNR_TREE_PORT16 && ctx->V > 0xFFFF)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: port16 needs V <= 65535 (V=%d)",
-                         ctx->V);
-    if (layout == SDNR_TREE_SLOT && ctx->V > (1 << 26) - 1)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: slots need V < 2^26 (V=%d)",
-                         ctx->V);
+    if ((rc = check_tree_layout(ctx, layout, to_root, name, "SDNR_MCAST_TO_ROOT"))) return rc;
     if ((ent_off == nullptr) != (ent_edge == nullptr))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: ent_off and ent_edge go together");
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: ent_off and ent_edge go together", name);
     if (ngroups == 0) return SDNR_OK;
-    if (!root || !mem_off) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: null pointer");
+    if (!root || !mem_off) return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
     SDNR_HIP(hipSetDevice(ctx->device));
     int64_t lo, hi, elo = 0, ehi = 0;
-    int rc = fetch_offset_ends(ctx, mem_off, ngroups, &lo, &hi);
-    if (rc) return rc;
-    if (lo < 0 || hi < lo)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: mem_off not monotone (mem_off[0]="
-                         "%lld, mem_off[%d]=%lld)", (long long)lo, ngroups, (long long)hi);
-    if (hi == lo || ctx->V == 0) return SDNR_OK;
+    bool empty;
+    if ((rc = list_bounds(ctx, mem_off, ngroups, name, "mem_off", &lo, &hi, &empty))) return rc;
+    if (empty || ctx->V == 0) return SDNR_OK;
     if (!tree || !mem_row || !mem_vertex)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: null pointer");
-    if (ent_off) {
-        if ((rc = fetch_offset_ends(ctx, ent_off, ngroups, &elo, &ehi))) return rc;
-        if (elo < 0 || ehi < elo)
-            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_multicast_trees: ent_off not monotone "
-                             "(ent_off[0]=%lld, ent_off[%d]=%lld)", (long long)elo, ngroups,
-                             (long long)ehi);
-    }
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
+    if (ent_off && (rc = list_bounds(ctx, ent_off, ngroups, name, "ent_off", &elo, &ehi)))
+        return rc;
     ctx->timed = (flags & SDNR_TIMING) != 0;
     return sdnr_launch_multicast_trees(ctx, tree, layout, to_root, nrows, ngroups, root, mem_off,
                                        lo, hi, mem_row, mem_vertex, weight, reached, ent_cnt,
@@ -1496,45 +1502,27 @@ int sdnr_fair_rates(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nro
                     int32_t *bott, int32_t *round, double *level, int32_t max_rounds, double *used,
                     int32_t *nrounds, uint32_t flags)
 {
+    static const char name[] = "sdnr_fair_rates";
     CHECK_CTX(ctx);
-    if (!nrounds) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_fair_rates: null nrounds");
+    if (!nrounds) return sdnr_fail(SDNR_ERR_INVAL, "%s: null nrounds", name);
     *nrounds = 0;
-    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_fair_rates: no graph uploaded");
-    if (!(flags & SDNR_DEVICE_PTRS))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_fair_rates: device pointers only");
-    if (nrows < 0 || nextra < 0 || max_rounds < 0)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_fair_rates: negative count");
-    if ((int64_t)ctx->E + nextra > 0x7FFFFFFF)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_fair_rates: E + nextra = %lld is no int32",
-                         (long long)ctx->E + nextra);
-    if (layout != SDNR_TREE_INT32 && layout != SDNR_TREE_PORT16 && layout != SDNR_TREE_SLOT)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_fair_rates: layout %d", layout);
-    const bool to_root = (flags & SDNR_LOADS_TO_ROOT) != 0;
-    if (to_root && layout != SDNR_TREE_INT32)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_fair_rates: SDNR_LOADS_TO_ROOT takes int32 "
-                         "next-hop rows (layout %d)", layout);
-    if (layout == SDNR_TREE_PORT16 && ctx->V > 0xFFFF)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_fair_rates: port16 needs V <= 65535 (V=%d)",
-                         ctx->V);
-    if (layout == SDNR_TREE_SLOT && ctx->V > (1 << 26) - 1)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_fair_rates: slots need V < 2^26 (V=%d)", ctx->V);
-    if (nrows == 0) return SDNR_OK;
-    if (!tree || !pair_off) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_fair_rates: null pointer");
-    SDNR_HIP(hipSetDevice(ctx->device));
-    // the bounds of the pair list: pair_off[0], pair_off[nrows] (two int64)
-    int w[4];
-    int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off), 2, w);
-    if (!rc) rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off + nrows), 2, w + 2);
+    int rc = open_pair_call(ctx, flags, nrows < 0 || nextra < 0 || max_rounds < 0, name);
     if (rc) return rc;
-    const int64_t lo = (int64_t)(((uint64_t)(uint32_t)w[1] << 32) | (uint32_t)w[0]);
-    const int64_t hi = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
-    if (lo < 0 || hi < lo)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_fair_rates: pair_off not monotone (pair_off[0]="
-                         "%lld, pair_off[%d]=%lld)", (long long)lo, nrows, (long long)hi);
-    if (hi == lo) return SDNR_OK;
+    if ((int64_t)ctx->E + nextra > 0x7FFFFFFF)
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: E + nextra = %lld is no int32", name,
+                         (long long)ctx->E + nextra);
+    const bool to_root = (flags & SDNR_LOADS_TO_ROOT) != 0;
+    if ((rc = check_tree_layout(ctx, layout, to_root, name, "SDNR_LOADS_TO_ROOT"))) return rc;
+    if (nrows == 0) return SDNR_OK;
+    if (!tree || !pair_off) return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
+    SDNR_HIP(hipSetDevice(ctx->device));
+    int64_t lo, hi;
+    bool empty;
+    if ((rc = list_bounds(ctx, pair_off, nrows, name, "pair_off", &lo, &hi, &empty))) return rc;
+    if (empty) return SDNR_OK;
     if (!verts || !rate || !bott || !round || (!level && max_rounds > 0) ||
         ((!cap || !used) && ctx->E + nextra > 0))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_fair_rates: null pointer");
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
     ctx->timed = (flags & SDNR_TIMING) != 0;
     return sdnr_launch_fair_rates(ctx, tree, layout, to_root, nrows, pair_off, lo, hi, verts, mult,
                                   extra, cap, nextra, rate, bott, round, level, max_rounds, used,
@@ -1547,36 +1535,25 @@ int sdnr_ecmp_fair_rates(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrows,
                          int32_t *bott, int32_t *round, double *level, int32_t max_rounds,
                          double *used, int32_t *nrounds, uint32_t flags)
 {
+    static const char name[] = "sdnr_ecmp_fair_rates";
     CHECK_CTX(ctx);
-    if (!nrounds) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: null nrounds");
+    if (!nrounds) return sdnr_fail(SDNR_ERR_INVAL, "%s: null nrounds", name);
     *nrounds = 0;
-    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_ecmp_fair_rates: no graph uploaded");
-    if (!(flags & SDNR_DEVICE_PTRS))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: device pointers only");
-    if (nrows < 0 || nextra < 0 || max_rounds < 0)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: negative count");
+    int rc = open_pair_call(ctx, flags, nrows < 0 || nextra < 0 || max_rounds < 0, name);
+    if (rc) return rc;
     if ((int64_t)ctx->E + nextra > 0x7FFFFFFF)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: E + nextra = %lld is no int32",
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: E + nextra = %lld is no int32", name,
                          (long long)ctx->E + nextra);
     if (nrows == 0) return SDNR_OK;
-    if (!pcost || !pair_off)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: null pointer");
+    if (!pcost || !pair_off) return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
     SDNR_HIP(hipSetDevice(ctx->device));
-    // the bounds of the pair list: pair_off[0], pair_off[nrows] (two int64)
-    int w[4];
-    int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off), 2, w);
-    if (!rc) rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off + nrows), 2, w + 2);
-    if (rc) return rc;
-    const int64_t lo = (int64_t)(((uint64_t)(uint32_t)w[1] << 32) | (uint32_t)w[0]);
-    const int64_t hi = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
-    if (lo < 0 || hi < lo)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: pair_off not monotone "
-                         "(pair_off[0]=%lld, pair_off[%d]=%lld)", (long long)lo, nrows,
-                         (long long)hi);
-    if (hi == lo) return SDNR_OK;
+    int64_t lo, hi;
+    bool empty;
+    if ((rc = list_bounds(ctx, pair_off, nrows, name, "pair_off", &lo, &hi, &empty))) return rc;
+    if (empty) return SDNR_OK;
     if (!srcs || !rate || !bott || !round || (!level && max_rounds > 0) ||
         ((!cap || !used) && ctx->E + nextra > 0))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: null pointer");
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
     ctx->timed = (flags & SDNR_TIMING) != 0;
     return sdnr_launch_ecmp_fair_rates(ctx, pcost, nrows, pair_off, lo, hi, srcs, mult, extra, cap,
                                        nextra, rate, bott, round, level, max_rounds, used, nrounds,
@@ -1587,28 +1564,18 @@ int sdnr_ecmp_link_loads(sdnr_ctx *ctx, const uint16_t *dist, int32_t nrows,
                          const int64_t *pair_off, const int32_t *srcs, const uint64_t *weight,
                          double *load, uint32_t flags)
 {
+    static const char name[] = "sdnr_ecmp_link_loads";
     CHECK_CTX(ctx);
-    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_ecmp_link_loads: no graph uploaded");
-    if (!(flags & SDNR_DEVICE_PTRS))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_link_loads: device pointers only");
-    if (nrows < 0) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_link_loads: negative count");
-    if (nrows == 0) return SDNR_OK;
-    if (!dist || !pair_off || !load)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_link_loads: null pointer");
-    SDNR_HIP(hipSetDevice(ctx->device));
-    // the bounds of the pair list: pair_off[0], pair_off[nrows] (two int64)
-    int w[4];
-    int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off), 2, w);
-    if (!rc) rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off + nrows), 2, w + 2);
+    int rc = open_pair_call(ctx, flags, nrows < 0, name);
     if (rc) return rc;
-    const int64_t lo = (int64_t)(((uint64_t)(uint32_t)w[1] << 32) | (uint32_t)w[0]);
-    const int64_t hi = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
-    if (lo < 0 || hi < lo)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_link_loads: pair_off not monotone "
-                         "(pair_off[0]=%lld, pair_off[%d]=%lld)", (long long)lo, nrows,
-                         (long long)hi);
-    if (hi == lo || ctx->V == 0) return SDNR_OK;
-    if (!srcs) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_link_loads: null pointer");
+    if (nrows == 0) return SDNR_OK;
+    if (!dist || !pair_off || !load) return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
+    SDNR_HIP(hipSetDevice(ctx->device));
+    int64_t lo, hi;
+    bool empty;
+    if ((rc = list_bounds(ctx, pair_off, nrows, name, "pair_off", &lo, &hi, &empty))) return rc;
+    if (empty || ctx->V == 0) return SDNR_OK;
+    if (!srcs) return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
     ctx->timed = (flags & SDNR_TIMING) != 0;
     return sdnr_launch_ecmp_link_loads(ctx, dist, nrows, pair_off, lo, hi, srcs, weight, load,
                                        (flags & SDNR_LOADS_SPLIT_HOP) != 0);
@@ -1694,47 +1661,24 @@ int sdnr_cost_ecmp_link_loads(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrow
                               const int64_t *pair_off, const int32_t *srcs,
                               const uint64_t *weight, double *load, uint32_t flags)
 {
+    static const char name[] = "sdnr_cost_ecmp_link_loads";
     CHECK_CTX(ctx);
-    if (ctx->V < 0)
-        return sdnr_fail(SDNR_ERR_STATE, "sdnr_cost_ecmp_link_loads: no graph uploaded");
-    if (!(flags & SDNR_DEVICE_PTRS))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_ecmp_link_loads: device pointers only");
-    if (nrows < 0) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_ecmp_link_loads: negative count");
-    if (!ctx->has_cost)
-        return sdnr_fail(SDNR_ERR_STATE, "sdnr_cost_ecmp_link_loads: no link costs uploaded for "
-                         "this graph (sdnr_graph_costs)");
-    if (nrows == 0) return SDNR_OK;
-    if (!pcost || !pair_off || !load)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_ecmp_link_loads: null pointer");
-    SDNR_HIP(hipSetDevice(ctx->device));
-    // the bounds of the pair list: pair_off[0], pair_off[nrows] (two int64)
-    int w[4];
-    int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off), 2, w);
-    if (!rc) rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(pair_off + nrows), 2, w + 2);
+    int rc = open_pair_call(ctx, flags, nrows < 0, name);
     if (rc) return rc;
-    const int64_t lo = (int64_t)(((uint64_t)(uint32_t)w[1] << 32) | (uint32_t)w[0]);
-    const int64_t hi = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
-    if (lo < 0 || hi < lo)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_ecmp_link_loads: pair_off not monotone "
-                         "(pair_off[0]=%lld, pair_off[%d]=%lld)", (long long)lo, nrows,
-                         (long long)hi);
-    if (hi == lo || ctx->V == 0) return SDNR_OK;
-    if (!srcs) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_ecmp_link_loads: null pointer");
+    if (!ctx->has_cost)
+        return sdnr_fail(SDNR_ERR_STATE, "%s: no link costs uploaded for this graph "
+                         "(sdnr_graph_costs)", name);
+    if (nrows == 0) return SDNR_OK;
+    if (!pcost || !pair_off || !load) return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
+    SDNR_HIP(hipSetDevice(ctx->device));
+    int64_t lo, hi;
+    bool empty;
+    if ((rc = list_bounds(ctx, pair_off, nrows, name, "pair_off", &lo, &hi, &empty))) return rc;
+    if (empty || ctx->V == 0) return SDNR_OK;
+    if (!srcs) return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
     ctx->timed = (flags & SDNR_TIMING) != 0;
     return sdnr_launch_cost_ecmp_link_loads(ctx, pcost, nrows, pair_off, lo, hi, srcs, weight,
                                             load, (flags & SDNR_LOADS_SPLIT_HOP) != 0);
-}
-
-// *lo, *hi = off[0], off[n] of a device int64 offset list
-static int fetch_bounds(sdnr_ctx *ctx, const int64_t *off, int32_t n, int64_t *lo, int64_t *hi)
-{
-    int w[4];
-    int rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(off), 2, w);
-    if (!rc) rc = sdnr_fetch_ints(ctx, reinterpret_cast<const int *>(off + n), 2, w + 2);
-    if (rc) return rc;
-    *lo = (int64_t)(((uint64_t)(uint32_t)w[1] << 32) | (uint32_t)w[0]);
-    *hi = (int64_t)(((uint64_t)(uint32_t)w[3] << 32) | (uint32_t)w[2]);
-    return SDNR_OK;
 }
 
 int sdnr_failure_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *dst, int32_t nrows,
@@ -1743,33 +1687,22 @@ int sdnr_failure_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *dst, int32_t nrow
                                  const int32_t *scen_edges, double *load, double *lost,
                                  uint8_t *routed, uint32_t flags)
 {
+    static const char name[] = "sdnr_failure_ecmp_link_loads";
     CHECK_CTX(ctx);
-    if (ctx->V < 0)
-        return sdnr_fail(SDNR_ERR_STATE, "sdnr_failure_ecmp_link_loads: no graph uploaded");
-    if (!(flags & SDNR_DEVICE_PTRS))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: device pointers only");
-    if (nrows < 0 || nscen < 0)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: negative count");
+    int rc = open_pair_call(ctx, flags, nrows < 0 || nscen < 0, name);
+    if (rc) return rc;
     if (nrows == 0 || nscen == 0) return SDNR_OK;
     if (!dst || !pair_off || !scen_off || !load)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: null pointer");
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
     SDNR_HIP(hipSetDevice(ctx->device));
     // the bounds of the pair list and of the failed-link list
     int64_t lo, hi, flo, fhi;
-    int rc = fetch_bounds(ctx, pair_off, nrows, &lo, &hi);
-    if (!rc) rc = fetch_bounds(ctx, scen_off, nscen, &flo, &fhi);
-    if (rc) return rc;
-    if (lo < 0 || hi < lo)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: pair_off not monotone "
-                         "(pair_off[0]=%lld, pair_off[%d]=%lld)", (long long)lo, nrows,
-                         (long long)hi);
-    if (flo < 0 || fhi < flo)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: scen_off not monotone "
-                         "(scen_off[0]=%lld, scen_off[%d]=%lld)", (long long)flo, nscen,
-                         (long long)fhi);
-    if (hi == lo || ctx->V == 0) return SDNR_OK;
+    bool empty;
+    if ((rc = list_bounds(ctx, pair_off, nrows, name, "pair_off", &lo, &hi, &empty))) return rc;
+    if ((rc = list_bounds(ctx, scen_off, nscen, name, "scen_off", &flo, &fhi))) return rc;
+    if (empty || ctx->V == 0) return SDNR_OK;
     if (!srcs || (fhi > flo && !scen_edges))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_failure_ecmp_link_loads: null pointer");
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
     ctx->timed = (flags & SDNR_TIMING) != 0;
     return sdnr_launch_failure_ecmp_link_loads(ctx, dst, nrows, pair_off, lo, hi, srcs, weight,
                                                nscen, scen_off, flo, fhi, scen_edges, load, lost,
@@ -1784,37 +1717,26 @@ int sdnr_whatif_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *dst, int32_t nrows
                                 const double *capacity, double *peak, int32_t *peak_edge,
                                 uint32_t flags)
 {
+    static const char name[] = "sdnr_whatif_ecmp_link_loads";
     CHECK_CTX(ctx);
-    if (ctx->V < 0)
-        return sdnr_fail(SDNR_ERR_STATE, "sdnr_whatif_ecmp_link_loads: no graph uploaded");
-    if (!(flags & SDNR_DEVICE_PTRS))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: device pointers only");
-    if (nrows < 0 || nscen < 0)
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: negative count");
+    int rc = open_pair_call(ctx, flags, nrows < 0 || nscen < 0, name);
+    if (rc) return rc;
     if ((peak == nullptr) != (peak_edge == nullptr))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: peak and peak_edge are "
-                         "both given or both NULL");
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: peak and peak_edge are both given or both NULL",
+                         name);
     if (nscen == 0) return SDNR_OK;
     if (!load || (nrows > 0 && (!dst || !pair_off || !scen_off)))
-        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: null pointer");
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
     SDNR_HIP(hipSetDevice(ctx->device));
     if (nrows > 0) {
         // the bounds of the pair list and of the override list
         int64_t lo, hi, flo, fhi;
-        int rc = fetch_bounds(ctx, pair_off, nrows, &lo, &hi);
-        if (!rc) rc = fetch_bounds(ctx, scen_off, nscen, &flo, &fhi);
-        if (rc) return rc;
-        if (lo < 0 || hi < lo)
-            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: pair_off not monotone "
-                             "(pair_off[0]=%lld, pair_off[%d]=%lld)", (long long)lo, nrows,
-                             (long long)hi);
-        if (flo < 0 || fhi < flo)
-            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: scen_off not monotone "
-                             "(scen_off[0]=%lld, scen_off[%d]=%lld)", (long long)flo, nscen,
-                             (long long)fhi);
-        if (hi > lo && ctx->V > 0) {
+        bool empty;
+        if ((rc = list_bounds(ctx, pair_off, nrows, name, "pair_off", &lo, &hi, &empty))) return rc;
+        if ((rc = list_bounds(ctx, scen_off, nscen, name, "scen_off", &flo, &fhi))) return rc;
+        if (!empty && ctx->V > 0) {
             if (!srcs || (fhi > flo && (!scen_edges || !scen_costs)))
-                return sdnr_fail(SDNR_ERR_INVAL, "sdnr_whatif_ecmp_link_loads: null pointer");
+                return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
             ctx->timed = (flags & SDNR_TIMING) != 0;
             rc = sdnr_launch_whatif_ecmp_link_loads(ctx, dst, nrows, pair_off, lo, hi, srcs,
                                                     weight, nscen, scen_off, flo, fhi, scen_edges,

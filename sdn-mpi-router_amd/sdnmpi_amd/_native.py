@@ -237,6 +237,11 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data) if a is not None else None
 
 
+def _p(address):
+    """A device or host address as a nullable pointer argument: 0 is NULL."""
+    return ctypes.c_void_p(address) if address else None
+
+
 class Context(object):
     """A route-engine context (owns graph + scratch) on one HIP device, or --
     ``device`` a sequence -- over several (sdnr_create_multi: the table calls
@@ -490,7 +495,7 @@ class Context(object):
         _check(self._lib.sdnr_dfs_rows_affected(
             self._h, ctypes.c_void_p(tree_ptr), ctypes.c_void_p(depth_ptr), int(layout),
             int(depth_bytes), int(nrows), ctypes.c_void_p(row_src_ptr),
-            ctypes.c_void_p(links_ptr) if links_ptr else None, int(nremoved), int(nadded),
+            _p(links_ptr), int(nremoved), int(nadded),
             ctypes.c_void_p(affected_ptr), flags))
 
     def link_loads_device(self, tree_ptr, layout, nrows, pair_off_ptr, dsts_ptr, weight_ptr,
@@ -501,11 +506,8 @@ class Context(object):
         every pair weighs 1; ``to_root``: next-hop rows (SDNR_LOADS_TO_ROOT)."""
         flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_TO_ROOT if to_root else 0)
         _check(self._lib.sdnr_link_loads(
-            self._h, ctypes.c_void_p(tree_ptr) if tree_ptr else None, int(layout), int(nrows),
-            ctypes.c_void_p(pair_off_ptr) if pair_off_ptr else None,
-            ctypes.c_void_p(dsts_ptr) if dsts_ptr else None,
-            ctypes.c_void_p(weight_ptr) if weight_ptr else None,
-            ctypes.c_void_p(load_ptr) if load_ptr else None, flags))
+            self._h, _p(tree_ptr), int(layout), int(nrows), _p(pair_off_ptr), _p(dsts_ptr),
+            _p(weight_ptr), _p(load_ptr), flags))
 
     def multicast_trees_device(self, tree_ptr, layout, nrows, ngroups, root_ptr, mem_off_ptr,
                                mem_row_ptr, mem_vertex_ptr, weight_ptr=0, reached_ptr=0,
@@ -519,12 +521,10 @@ class Context(object):
         into by the call that gets it, ``weight_ptr`` 0: every group weighs 1;
         ``reached_ptr``: u8 per member.  Pointers that are 0 are left out."""
         flags = DEVICE_PTRS | (TIMING if timing else 0) | (MCAST_TO_ROOT if to_root else 0)
-        p = [ctypes.c_void_p(x) if x else None
-             for x in (root_ptr, mem_off_ptr, mem_row_ptr, mem_vertex_ptr, weight_ptr, reached_ptr,
-                       ent_cnt_ptr, ent_off_ptr, ent_edge_ptr, load_ptr)]
+        p = [_p(x) for x in (root_ptr, mem_off_ptr, mem_row_ptr, mem_vertex_ptr, weight_ptr,
+                             reached_ptr, ent_cnt_ptr, ent_off_ptr, ent_edge_ptr, load_ptr)]
         _check(self._lib.sdnr_multicast_trees(
-            self._h, ctypes.c_void_p(tree_ptr) if tree_ptr else None, int(layout), int(nrows),
-            int(ngroups), *(p + [flags])))
+            self._h, _p(tree_ptr), int(layout), int(nrows), int(ngroups), *(p + [flags])))
 
     def ecmp_link_loads_device(self, dist_ptr, nrows, pair_off_ptr, srcs_ptr, weight_ptr,
                                load_ptr, hop=False, timing=False):
@@ -535,11 +535,8 @@ class Context(object):
         evenly per switch (SDNR_LOADS_SPLIT_HOP) instead of per route."""
         flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_SPLIT_HOP if hop else 0)
         _check(self._lib.sdnr_ecmp_link_loads(
-            self._h, ctypes.c_void_p(dist_ptr) if dist_ptr else None, int(nrows),
-            ctypes.c_void_p(pair_off_ptr) if pair_off_ptr else None,
-            ctypes.c_void_p(srcs_ptr) if srcs_ptr else None,
-            ctypes.c_void_p(weight_ptr) if weight_ptr else None,
-            ctypes.c_void_p(load_ptr) if load_ptr else None, flags))
+            self._h, _p(dist_ptr), int(nrows), _p(pair_off_ptr), _p(srcs_ptr), _p(weight_ptr),
+            _p(load_ptr), flags))
 
     def cost_ecmp_link_loads_device(self, pcost_ptr, nrows, pair_off_ptr, srcs_ptr, weight_ptr,
                                     load_ptr, hop=False, timing=False):
@@ -551,11 +548,8 @@ class Context(object):
         switch (SDNR_LOADS_SPLIT_HOP) instead of per route."""
         flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_SPLIT_HOP if hop else 0)
         _check(self._lib.sdnr_cost_ecmp_link_loads(
-            self._h, ctypes.c_void_p(pcost_ptr) if pcost_ptr else None, int(nrows),
-            ctypes.c_void_p(pair_off_ptr) if pair_off_ptr else None,
-            ctypes.c_void_p(srcs_ptr) if srcs_ptr else None,
-            ctypes.c_void_p(weight_ptr) if weight_ptr else None,
-            ctypes.c_void_p(load_ptr) if load_ptr else None, flags))
+            self._h, _p(pcost_ptr), int(nrows), _p(pair_off_ptr), _p(srcs_ptr), _p(weight_ptr),
+            _p(load_ptr), flags))
 
     def failure_ecmp_link_loads_device(self, dst_ptr, nrows, pair_off_ptr, srcs_ptr, weight_ptr,
                                        nscen, scen_off_ptr, scen_edges_ptr, load_ptr, lost_ptr=0,
@@ -570,11 +564,10 @@ class Context(object):
         uploaded: every link costs 1).  ``weight_ptr`` 0: every pair weighs 1;
         ``hop``: split evenly per switch (SDNR_LOADS_SPLIT_HOP)."""
         flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_SPLIT_HOP if hop else 0)
-        p = lambda a: ctypes.c_void_p(a) if a else None    # noqa: E731
         _check(self._lib.sdnr_failure_ecmp_link_loads(
-            self._h, p(dst_ptr), int(nrows), p(pair_off_ptr), p(srcs_ptr), p(weight_ptr),
-            int(nscen), p(scen_off_ptr), p(scen_edges_ptr), p(load_ptr), p(lost_ptr),
-            p(routed_ptr), flags))
+            self._h, _p(dst_ptr), int(nrows), _p(pair_off_ptr), _p(srcs_ptr), _p(weight_ptr),
+            int(nscen), _p(scen_off_ptr), _p(scen_edges_ptr), _p(load_ptr), _p(lost_ptr),
+            _p(routed_ptr), flags))
 
     def whatif_ecmp_link_loads_device(self, dst_ptr, nrows, pair_off_ptr, srcs_ptr, weight_ptr,
                                       nscen, scen_off_ptr, scen_edges_ptr, scen_costs_ptr,
@@ -591,11 +584,10 @@ class Context(object):
         1.0 per link) and the first link that attains it:
         sdnr_whatif_ecmp_link_loads, device pointers, asynchronous."""
         flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_SPLIT_HOP if hop else 0)
-        p = lambda a: ctypes.c_void_p(a) if a else None    # noqa: E731
         _check(self._lib.sdnr_whatif_ecmp_link_loads(
-            self._h, p(dst_ptr), int(nrows), p(pair_off_ptr), p(srcs_ptr), p(weight_ptr),
-            int(nscen), p(scen_off_ptr), p(scen_edges_ptr), p(scen_costs_ptr), p(load_ptr),
-            p(lost_ptr), p(routed_ptr), p(capacity_ptr), p(peak_ptr), p(peak_edge_ptr), flags))
+            self._h, _p(dst_ptr), int(nrows), _p(pair_off_ptr), _p(srcs_ptr), _p(weight_ptr),
+            int(nscen), _p(scen_off_ptr), _p(scen_edges_ptr), _p(scen_costs_ptr), _p(load_ptr),
+            _p(lost_ptr), _p(routed_ptr), _p(capacity_ptr), _p(peak_ptr), _p(peak_edge_ptr), flags))
 
     def lfa_tables_device(self, pcost_all_ptr, dst_ptr, ndst, backup_ptr, backup_port_ptr,
                           kind_ptr, counts_ptr=0, link_only=False, timing=False):
@@ -608,10 +600,9 @@ class Context(object):
         [ndst][4] (primaries, backups, node-protecting, downstream).
         ``link_only``: SDNR_LFA_LINK_ONLY."""
         flags = DEVICE_PTRS | (TIMING if timing else 0) | (LFA_LINK_ONLY if link_only else 0)
-        p = lambda a: ctypes.c_void_p(a) if a else None    # noqa: E731
         _check(self._lib.sdnr_lfa_tables(
-            self._h, p(pcost_all_ptr), p(dst_ptr), int(ndst), p(backup_ptr), p(backup_port_ptr),
-            p(kind_ptr), p(counts_ptr), flags))
+            self._h, _p(pcost_all_ptr), _p(dst_ptr), int(ndst), _p(backup_ptr), _p(backup_port_ptr),
+            _p(kind_ptr), _p(counts_ptr), flags))
 
     def apsp(self):
         dist = np.empty((self.V, self.V), np.uint16)
@@ -624,7 +615,7 @@ class Context(object):
         flags = DEVICE_PTRS | (TIMING if timing else 0)
         _check(self._lib.sdnr_dfs_tables(
             self._h, ctypes.c_void_p(src_ptr), int(nsrc), ctypes.c_void_p(parent_ptr),
-            ctypes.c_void_p(port_ptr), ctypes.c_void_p(hops_ptr) if hops_ptr else None,
+            ctypes.c_void_p(port_ptr), _p(hops_ptr),
             flags))
 
     def dfs_tables_packed_device(self, src_ptr, nsrc, tree_ptr, timing=False):
@@ -645,7 +636,7 @@ class Context(object):
         flags = DEVICE_PTRS | (TIMING if timing else 0)
         _check(self._lib.sdnr_dfs_tables_tree(
             self._h, ctypes.c_void_p(src_ptr), int(nsrc), ctypes.c_void_p(tree_ptr),
-            ctypes.c_void_p(depth_ptr) if depth_ptr else None, int(layout), int(depth_bytes),
+            _p(depth_ptr), int(layout), int(depth_bytes),
             flags))
 
     def dfs_tables_tree(self, srcs, layout, depth_bytes=2):
@@ -662,17 +653,15 @@ class Context(object):
     def tree_pack_device(self, parent_ptr, port_ptr, n, tree_ptr, layout):
         """int32 parent/port tables (device) -> 4-byte trees (sdnr_tree_pack)."""
         _check(self._lib.sdnr_tree_pack(self._h, ctypes.c_void_p(parent_ptr),
-                                        ctypes.c_void_p(port_ptr) if port_ptr else None,
-                                        int(n), ctypes.c_void_p(tree_ptr), int(layout),
-                                        DEVICE_PTRS))
+                                        _p(port_ptr), int(n), ctypes.c_void_p(tree_ptr),
+                                        int(layout), DEVICE_PTRS))
 
     def shortest_tables_device(self, dst_ptr, ndst, dist_ptr, nh_ptr=0, nh_port_ptr=0,
                                timing=False):
         flags = DEVICE_PTRS | (TIMING if timing else 0)
         _check(self._lib.sdnr_shortest_tables(
             self._h, ctypes.c_void_p(dst_ptr), int(ndst), ctypes.c_void_p(dist_ptr),
-            ctypes.c_void_p(nh_ptr) if nh_ptr else None,
-            ctypes.c_void_p(nh_port_ptr) if nh_port_ptr else None, flags))
+            _p(nh_ptr), _p(nh_port_ptr), flags))
 
     def cost_tables_device(self, dst_ptr, ndst, pcost_ptr, nh_ptr=0, nh_port_ptr=0,
                            timing=False):
@@ -681,8 +670,7 @@ class Context(object):
         flags = DEVICE_PTRS | (TIMING if timing else 0)
         _check(self._lib.sdnr_cost_tables(
             self._h, ctypes.c_void_p(dst_ptr), int(ndst), ctypes.c_void_p(pcost_ptr),
-            ctypes.c_void_p(nh_ptr) if nh_ptr else None,
-            ctypes.c_void_p(nh_port_ptr) if nh_port_ptr else None, flags))
+            _p(nh_ptr), _p(nh_port_ptr), flags))
 
     def widest_tables_device(self, pcost_ptr, util_ptr, dst_ptr, ndst, bott_ptr, nh_ptr=0,
                              nh_port_ptr=0, timing=False):
@@ -690,10 +678,9 @@ class Context(object):
         nh_port int32 [ndst][V]; util u32 [E]; both next-hop pointers or
         neither), asynchronous."""
         flags = DEVICE_PTRS | (TIMING if timing else 0)
-        p = lambda a: ctypes.c_void_p(a) if a else None    # noqa: E731
         _check(self._lib.sdnr_widest_tables(
-            self._h, p(pcost_ptr), p(util_ptr), p(dst_ptr), int(ndst), p(bott_ptr), p(nh_ptr),
-            p(nh_port_ptr), flags))
+            self._h, _p(pcost_ptr), _p(util_ptr), _p(dst_ptr), int(ndst), _p(bott_ptr), _p(nh_ptr),
+            _p(nh_port_ptr), flags))
 
     def fair_rates_device(self, tree_ptr, layout, nrows, pair_off_ptr, verts_ptr, mult_ptr,
                           extra_ptr, cap_ptr, nextra, rate_ptr, bott_ptr, round_ptr, level_ptr,
@@ -706,12 +693,11 @@ class Context(object):
         rows (SDNR_LOADS_TO_ROOT).  Waits for the rounds; errors of the rows
         surface in ``synchronize``."""
         flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_TO_ROOT if to_root else 0)
-        p = lambda a: ctypes.c_void_p(a) if a else None    # noqa: E731
         n = ctypes.c_int32()
         _check(self._lib.sdnr_fair_rates(
-            self._h, p(tree_ptr), int(layout), int(nrows), p(pair_off_ptr), p(verts_ptr),
-            p(mult_ptr), p(extra_ptr), p(cap_ptr), int(nextra), p(rate_ptr), p(bott_ptr),
-            p(round_ptr), p(level_ptr), int(max_rounds), p(used_ptr), ctypes.byref(n), flags))
+            self._h, _p(tree_ptr), int(layout), int(nrows), _p(pair_off_ptr), _p(verts_ptr),
+            _p(mult_ptr), _p(extra_ptr), _p(cap_ptr), int(nextra), _p(rate_ptr), _p(bott_ptr),
+            _p(round_ptr), _p(level_ptr), int(max_rounds), _p(used_ptr), ctypes.byref(n), flags))
         return n.value
 
     def ecmp_fair_rates_device(self, pcost_ptr, nrows, pair_off_ptr, srcs_ptr, mult_ptr,
@@ -726,12 +712,11 @@ class Context(object):
         constraints; ``hop``: SDNR_LOADS_SPLIT_HOP.  Waits for the rounds;
         errors of the rows surface in ``synchronize``."""
         flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_SPLIT_HOP if hop else 0)
-        p = lambda a: ctypes.c_void_p(a) if a else None    # noqa: E731
         n = ctypes.c_int32()
         _check(self._lib.sdnr_ecmp_fair_rates(
-            self._h, p(pcost_ptr), int(nrows), p(pair_off_ptr), p(srcs_ptr), p(mult_ptr),
-            p(extra_ptr), p(cap_ptr), int(nextra), p(rate_ptr), p(bott_ptr), p(round_ptr),
-            p(level_ptr), int(max_rounds), p(used_ptr), ctypes.byref(n), flags))
+            self._h, _p(pcost_ptr), int(nrows), _p(pair_off_ptr), _p(srcs_ptr), _p(mult_ptr),
+            _p(extra_ptr), _p(cap_ptr), int(nextra), _p(rate_ptr), _p(bott_ptr), _p(round_ptr),
+            _p(level_ptr), int(max_rounds), _p(used_ptr), ctypes.byref(n), flags))
         return n.value
 
     def apsp_device(self, dist_ptr, timing=False):

@@ -268,6 +268,38 @@ def _pairs_by_row(rows, nrows):
     return order, off
 
 
+def _pairs_for_device(rows, nrows, verts, V, weights, what, table="the table"):
+    """The pair list of a row-grouped entry point, pure numpy: ``(order, off,
+    verts_i32, weights_u64_or_None)`` -- ``_pairs_by_row``'s order and offsets,
+    the pairs' vertices in that order (int32, -1 for one outside [0, V)) and
+    their weights in that order (None stays None).  A row outside [0, nrows)
+    raises in the caller's name ``what``."""
+    rows = np.asarray(rows, np.int64).reshape(-1)
+    if rows.size and (rows.min() < 0 or rows.max() >= nrows):
+        raise ValueError("%s: a pair names a row outside %s" % (what, table))
+    order, off = _pairs_by_row(rows, nrows)
+    x = np.asarray(verts, np.int64).reshape(-1)[order]
+    x = np.where((x < 0) | (x >= V), -1, x).astype(np.int32)
+    if weights is not None:
+        weights = np.ascontiguousarray(np.asarray(weights, np.uint64).reshape(-1)[order])
+    return order, off, x, weights
+
+
+def _unsorted(a, order):
+    """``a`` (numpy, in ``_pairs_by_row``'s order along its last axis) back in
+    the caller's order."""
+    if isinstance(order, slice):
+        return a
+    back = np.empty_like(a)
+    back[..., order] = a
+    return back
+
+
+def _ptr(a):
+    """The device address of a tensor, 0 for None."""
+    return a.data_ptr() if a is not None else 0
+
+
 def _gather(a, r, c):
     """a[r[i], c[i]] of a [k, V] table (numpy or device tensor) as numpy."""
     if _is_np(a):
@@ -1617,14 +1649,44 @@ class RouteEngine(object):
         tl = self._torch.from_numpy(links.astype(np.int32)).to(self.dev)
         ts = self._ids(row_src)
         out = t.empty(n, dtype=t.uint8, device=self.dev)
-        lay = {PORT16: _native.TREE_PORT16, SLOT: _native.TREE_SLOT,
-               INT32: _native.TREE_INT32}[layout]
+        lay = self._layout_code(layout)
         self._ready()
         self.ctx.dfs_rows_affected_device(tree.data_ptr(), depth.data_ptr(), lay,
                                           depth.element_size(), n, ts.data_ptr(),
                                           tl.data_ptr(), nrm, nadd, out.data_ptr())
         self.ctx.synchronize()              # raises if a row was not a tree
         return out.cpu().numpy().astype(bool)
+
+    def _use_costs(self, export, cost):
+        """Load ``export`` with the link costs ``cost`` in force; None clears
+        the context's costs (every link costs 1)."""
+        if cost is None:
+            self.load(export)
+            if self._costs is not None:
+                self._costs = None
+                self.ctx.set_link_costs(None)
+        else:
+            self.set_link_costs(export, cost)
+
+    def _pcost_device(self, pcost):
+        """``pcost`` rows as a device tensor (int32 holding u32): a numpy array
+        is uploaded, a tensor passes."""
+        if _is_np(pcost):
+            return self._torch.from_numpy(
+                np.ascontiguousarray(_pcost_u32(pcost)).view(np.int32)).to(self.dev)
+        return pcost
+
+    @staticmethod
+    def _layout_code(layout):
+        return {PORT16: _native.TREE_PORT16, SLOT: _native.TREE_SLOT,
+                INT32: _native.TREE_INT32}[layout]
+
+    def _upload_pairs(self, off, verts, weights):
+        """``_pairs_for_device``'s arrays as device tensors (the u64 weights
+        in an int64 tensor, None stays None)."""
+        t = self._torch
+        d_w = None if weights is None else t.from_numpy(weights.view(np.int64)).to(self.dev)
+        return t.from_numpy(off).to(self.dev), t.from_numpy(verts).to(self.dev), d_w
 
     def link_loads(self, export, tree, layout, rows, dsts, weights=None, to_root=False,
                    timing=False):
@@ -1644,26 +1706,15 @@ class RouteEngine(object):
         nrows = int(tree.shape[0])
         if rows.size == 0 or nrows == 0 or E == 0:
             return np.zeros(E, np.uint64)
-        if rows.min() < 0 or rows.max() >= nrows:
-            raise ValueError("link_loads: a pair names a row outside the table")
-        order, off = _pairs_by_row(rows, nrows)
-        V = int(export.csr.V)
-        d = np.asarray(dsts, np.int64)[order]
-        d = np.where((d < 0) | (d >= V), -1, d).astype(np.int32)
+        order, off, d, w = _pairs_for_device(rows, nrows, dsts, int(export.csr.V), weights,
+                                             "link_loads")
         tree = tree.contiguous()
-        d_off = t.from_numpy(off).to(self.dev)
-        d_dst = t.from_numpy(d).to(self.dev)
-        d_w = None
-        if weights is not None:
-            w = np.ascontiguousarray(np.asarray(weights, np.uint64)[order])
-            d_w = t.from_numpy(w.view(np.int64)).to(self.dev)
+        d_off, d_dst, d_w = self._upload_pairs(off, d, w)
         load = t.zeros(E, dtype=t.int64, device=self.dev)
-        lay = {PORT16: _native.TREE_PORT16, SLOT: _native.TREE_SLOT,
-               INT32: _native.TREE_INT32}[layout]
+        lay = self._layout_code(layout)
         self._ready()
         self.ctx.link_loads_device(tree.data_ptr(), lay, nrows, d_off.data_ptr(), d_dst.data_ptr(),
-                                   d_w.data_ptr() if d_w is not None else 0, load.data_ptr(),
-                                   to_root=to_root, timing=timing)
+                                   _ptr(d_w), load.data_ptr(), to_root=to_root, timing=timing)
         self.ctx.synchronize()              # raises if a row was not a tree
         return load.cpu().numpy().view(np.uint64)
 
@@ -1713,14 +1764,12 @@ class RouteEngine(object):
         d_reach = t.zeros(nmem, dtype=t.uint8, device=self.dev)
         d_cnt = t.zeros(ng, dtype=t.int64, device=self.dev)
         d_load = t.zeros(max(E, 1), dtype=t.int64, device=self.dev) if loads else None
-        lay = {PORT16: _native.TREE_PORT16, SLOT: _native.TREE_SLOT,
-               INT32: _native.TREE_INT32}[layout]
+        lay = self._layout_code(layout)
         self._ready()
         self.ctx.multicast_trees_device(
             tree.data_ptr(), lay, nrows, ng, d_root.data_ptr(), d_off.data_ptr(),
-            d_row.data_ptr(), d_ver.data_ptr(), d_w.data_ptr() if d_w is not None else 0,
-            d_reach.data_ptr(), d_cnt.data_ptr(), 0, 0,
-            d_load.data_ptr() if d_load is not None else 0, to_root=to_root, timing=True)
+            d_row.data_ptr(), d_ver.data_ptr(), _ptr(d_w), d_reach.data_ptr(), d_cnt.data_ptr(),
+            0, 0, _ptr(d_load), to_root=to_root, timing=True)
         self.ctx.synchronize()              # raises if a row was not a tree
         self.last_multicast_ms += self.ctx.last_kernel_ms()
         d_eoff = t.zeros(ng + 1, dtype=t.int64, device=self.dev)
@@ -1756,60 +1805,10 @@ class RouteEngine(object):
         (None: 1.0 per link, no extras).  The flows are sorted by row here and
         every row stays on the device across the rounds."""
         self.load(export)
-        t = self._torch
-        V, E = int(export.csr.V), int(export.csr.E)
-        rows = np.asarray(rows, np.int64).reshape(-1)
-        n = rows.shape[0]
-        if cap is None:
-            cap = np.ones(E, np.float64)
-        mult_in = mult
-        mult, cap, extra_all, nextra = check_fair_flows(E, n, mult, cap, extra)
-        NE = E + nextra
-        nrows = int(tree.shape[0])
-        if n == 0 or nrows == 0:
-            if n:
-                raise ValueError("fair_rates: a pair names a row outside the table")
-            return (np.zeros(0, np.float64), np.zeros(0, np.int32), np.zeros(0, np.int32),
-                    np.zeros(0, np.float64), np.zeros(NE, np.float64))
-        if rows.min() < 0 or rows.max() >= nrows:
-            raise ValueError("fair_rates: a pair names a row outside the table")
-        order, off = _pairs_by_row(rows, nrows)
-        x = np.asarray(verts, np.int64).reshape(-1)[order]
-        x = np.where((x < 0) | (x >= V), -1, x).astype(np.int32)
-        tree = tree.contiguous()
-        d_off = t.from_numpy(off).to(self.dev)
-        d_x = t.from_numpy(x).to(self.dev)
-        d_m = d_e = None
-        if mult_in is not None:
-            d_m = t.from_numpy(np.ascontiguousarray(mult[order]).view(np.int64)).to(self.dev)
-        if extra is not None:
-            d_e = t.from_numpy(np.ascontiguousarray(extra_all[order].astype(np.int32))).to(self.dev)
-        d_cap = t.from_numpy(cap).to(self.dev)
-        max_rounds = min(n, NE)
-        rate = t.empty(n, dtype=t.float64, device=self.dev)
-        bott = t.empty(n, dtype=t.int32, device=self.dev)
-        rnd = t.empty(n, dtype=t.int32, device=self.dev)
-        level = t.empty(max_rounds, dtype=t.float64, device=self.dev)
-        used = t.zeros(NE, dtype=t.float64, device=self.dev)
-        lay = {PORT16: _native.TREE_PORT16, SLOT: _native.TREE_SLOT,
-               INT32: _native.TREE_INT32}[layout]
-        self._ready()
-        rounds = self.ctx.fair_rates_device(
-            tree.data_ptr(), lay, nrows, d_off.data_ptr(), d_x.data_ptr(),
-            d_m.data_ptr() if d_m is not None else 0, d_e.data_ptr() if d_e is not None else 0,
-            d_cap.data_ptr() if NE else 0, nextra, rate.data_ptr(), bott.data_ptr(),
-            rnd.data_ptr(), level.data_ptr() if max_rounds else 0, max_rounds,
-            used.data_ptr() if NE else 0, to_root=to_root, timing=timing)
-        self.ctx.synchronize()              # raises if a row was not a tree
-        out = []
-        for a in (rate, bott, rnd):
-            a = a.cpu().numpy()
-            if not isinstance(order, slice):
-                back = np.empty_like(a)
-                back[order] = a
-                a = back
-            out.append(a)
-        return out[0], out[1], out[2], level.cpu().numpy()[:rounds], used.cpu().numpy()
+        return self._fair_rates_over(
+            "fair_rates", export, tree, rows, verts, mult, cap, extra,
+            lambda tree, *a: self.ctx.fair_rates_device(tree, self._layout_code(layout), *a,
+                                                        to_root=to_root, timing=timing))
 
     def ecmp_fair_rates(self, export, cost, pcost, rows, srcs, mult=None, cap=None, extra=None,
                         split="route", timing=False):
@@ -1827,13 +1826,19 @@ class RouteEngine(object):
         on the device across the rounds."""
         if split not in SPLITS:
             raise ValueError("split must be 'route' or 'hop'")
-        if cost is None:
-            self.load(export)
-            if self._costs is not None:
-                self._costs = None
-                self.ctx.set_link_costs(None)
-        else:
-            self.set_link_costs(export, cost)
+        self._use_costs(export, cost)
+        return self._fair_rates_over(
+            "ecmp_fair_rates", export, self._pcost_device(pcost), rows, srcs, mult, cap, extra,
+            lambda pc, *a: self.ctx.ecmp_fair_rates_device(pc, *a, hop=split == "hop",
+                                                           timing=timing),
+            word=4)
+
+    def _fair_rates_over(self, what, export, table, rows, verts, mult, cap, extra, launch,
+                         word=None):
+        """``fair_rates`` and ``ecmp_fair_rates`` after their table argument:
+        ``table`` is the [k, V] device tensor the flows' rows index (``word``:
+        the element size it must have) and ``launch(table pointer, nrows,
+        ...)`` the entry point, which returns the number of rounds."""
         t = self._torch
         V, E = int(export.csr.V), int(export.csr.E)
         rows = np.asarray(rows, np.int64).reshape(-1)
@@ -1843,28 +1848,19 @@ class RouteEngine(object):
         mult_in = mult
         mult, cap, extra_all, nextra = check_fair_flows(E, n, mult, cap, extra)
         NE = E + nextra
-        if isinstance(pcost, np.ndarray):
-            pcost = t.from_numpy(np.ascontiguousarray(_pcost_u32(pcost)).view(np.int32)).to(
-                self.dev)
-        nrows = int(pcost.shape[0])
+        nrows = int(table.shape[0])
         if n == 0 or nrows == 0:
             if n:
-                raise ValueError("ecmp_fair_rates: a pair names a row outside the table")
+                raise ValueError("%s: a pair names a row outside the table" % what)
             return (np.zeros(0, np.float64), np.zeros(0, np.int32), np.zeros(0, np.int32),
                     np.zeros(0, np.float64), np.zeros(NE, np.float64))
-        if rows.min() < 0 or rows.max() >= nrows:
-            raise ValueError("ecmp_fair_rates: a pair names a row outside the table")
-        if pcost.element_size() != 4:
-            raise ValueError("ecmp_fair_rates: pcost rows are 32-bit")
-        order, off = _pairs_by_row(rows, nrows)
-        x = np.asarray(srcs, np.int64).reshape(-1)[order]
-        x = np.where((x < 0) | (x >= V), -1, x).astype(np.int32)
-        pcost = pcost.contiguous()
-        d_off = t.from_numpy(off).to(self.dev)
-        d_x = t.from_numpy(x).to(self.dev)
-        d_m = d_e = None
-        if mult_in is not None:
-            d_m = t.from_numpy(np.ascontiguousarray(mult[order]).view(np.int64)).to(self.dev)
+        order, off, x, m = _pairs_for_device(rows, nrows, verts, V,
+                                             None if mult_in is None else mult, what)
+        if word is not None and table.element_size() != word:
+            raise ValueError("%s: pcost rows are 32-bit" % what)
+        table = table.contiguous()
+        d_off, d_x, d_m = self._upload_pairs(off, x, m)
+        d_e = None
         if extra is not None:
             d_e = t.from_numpy(np.ascontiguousarray(extra_all[order].astype(np.int32))).to(self.dev)
         d_cap = t.from_numpy(cap).to(self.dev)
@@ -1875,22 +1871,14 @@ class RouteEngine(object):
         level = t.empty(max_rounds, dtype=t.float64, device=self.dev)
         used = t.zeros(NE, dtype=t.float64, device=self.dev)
         self._ready()
-        rounds = self.ctx.ecmp_fair_rates_device(
-            pcost.data_ptr(), nrows, d_off.data_ptr(), d_x.data_ptr(),
-            d_m.data_ptr() if d_m is not None else 0, d_e.data_ptr() if d_e is not None else 0,
+        rounds = launch(
+            table.data_ptr(), nrows, d_off.data_ptr(), d_x.data_ptr(), _ptr(d_m), _ptr(d_e),
             d_cap.data_ptr() if NE else 0, nextra, rate.data_ptr(), bott.data_ptr(),
             rnd.data_ptr(), level.data_ptr() if max_rounds else 0, max_rounds,
-            used.data_ptr() if NE else 0, hop=split == "hop", timing=timing)
-        self.ctx.synchronize()              # raises if a row was no least-cost labelling
-        out = []
-        for a in (rate, bott, rnd):
-            a = a.cpu().numpy()
-            if not isinstance(order, slice):
-                back = np.empty_like(a)
-                back[order] = a
-                a = back
-            out.append(a)
-        return out[0], out[1], out[2], level.cpu().numpy()[:rounds], used.cpu().numpy()
+            used.data_ptr() if NE else 0)
+        self.ctx.synchronize()              # raises if a row was no tree / least-cost labelling
+        rate, bott, rnd = (_unsorted(a.cpu().numpy(), order) for a in (rate, bott, rnd))
+        return rate, bott, rnd, level.cpu().numpy()[:rounds], used.cpu().numpy()
 
     def ecmp_link_loads(self, export, dist, rows, srcs, weights=None, split="route",
                         timing=False):
@@ -1915,27 +1903,17 @@ class RouteEngine(object):
         nrows = int(dist.shape[0])
         if rows.size == 0 or nrows == 0 or E == 0:
             return np.zeros(E, np.float64)
-        if rows.min() < 0 or rows.max() >= nrows:
-            raise ValueError("ecmp_link_loads: a pair names a row outside the table")
+        order, off, s, w = _pairs_for_device(rows, nrows, srcs, int(export.csr.V), weights,
+                                             "ecmp_link_loads")
         if dist.element_size() != 2:
             raise ValueError("ecmp_link_loads: distance rows are 16-bit")
-        order, off = _pairs_by_row(rows, nrows)
-        V = int(export.csr.V)
-        s = np.asarray(srcs, np.int64)[order]
-        s = np.where((s < 0) | (s >= V), -1, s).astype(np.int32)
         dist = dist.contiguous()
-        d_off = t.from_numpy(off).to(self.dev)
-        d_src = t.from_numpy(s).to(self.dev)
-        d_w = None
-        if weights is not None:
-            w = np.ascontiguousarray(np.asarray(weights, np.uint64)[order])
-            d_w = t.from_numpy(w.view(np.int64)).to(self.dev)
+        d_off, d_src, d_w = self._upload_pairs(off, s, w)
         load = t.zeros(E, dtype=t.float64, device=self.dev)
         self._ready()
         self.ctx.ecmp_link_loads_device(dist.data_ptr(), nrows, d_off.data_ptr(),
-                                        d_src.data_ptr(),
-                                        d_w.data_ptr() if d_w is not None else 0,
-                                        load.data_ptr(), hop=split == "hop", timing=timing)
+                                        d_src.data_ptr(), _ptr(d_w), load.data_ptr(),
+                                        hop=split == "hop", timing=timing)
         self.ctx.synchronize()              # raises if a row was no BFS labelling
         return load.cpu().numpy()
 
@@ -1958,33 +1936,21 @@ class RouteEngine(object):
         t = self._torch
         E = int(export.csr.E)
         rows = np.asarray(rows, np.int64)
-        if isinstance(pcost, np.ndarray):
-            pcost = t.from_numpy(np.ascontiguousarray(_pcost_u32(pcost)).view(np.int32)).to(
-                self.dev)
+        pcost = self._pcost_device(pcost)
         nrows = int(pcost.shape[0])
         if rows.size == 0 or nrows == 0 or E == 0:
             return np.zeros(E, np.float64)
-        if rows.min() < 0 or rows.max() >= nrows:
-            raise ValueError("cost_ecmp_link_loads: a pair names a row outside the table")
+        order, off, s, w = _pairs_for_device(rows, nrows, srcs, int(export.csr.V), weights,
+                                             "cost_ecmp_link_loads")
         if pcost.element_size() != 4:
             raise ValueError("cost_ecmp_link_loads: pcost rows are 32-bit")
-        order, off = _pairs_by_row(rows, nrows)
-        V = int(export.csr.V)
-        s = np.asarray(srcs, np.int64)[order]
-        s = np.where((s < 0) | (s >= V), -1, s).astype(np.int32)
         pcost = pcost.contiguous()
-        d_off = t.from_numpy(off).to(self.dev)
-        d_src = t.from_numpy(s).to(self.dev)
-        d_w = None
-        if weights is not None:
-            w = np.ascontiguousarray(np.asarray(weights, np.uint64)[order])
-            d_w = t.from_numpy(w.view(np.int64)).to(self.dev)
+        d_off, d_src, d_w = self._upload_pairs(off, s, w)
         load = t.zeros(E, dtype=t.float64, device=self.dev)
         self._ready()
         self.ctx.cost_ecmp_link_loads_device(pcost.data_ptr(), nrows, d_off.data_ptr(),
-                                             d_src.data_ptr(),
-                                             d_w.data_ptr() if d_w is not None else 0,
-                                             load.data_ptr(), hop=split == "hop", timing=timing)
+                                             d_src.data_ptr(), _ptr(d_w), load.data_ptr(),
+                                             hop=split == "hop", timing=timing)
         self.ctx.synchronize()              # raises if a row was no least-cost labelling
         return load.cpu().numpy()
 
@@ -2009,13 +1975,7 @@ class RouteEngine(object):
         not bit-reproducible."""
         if split not in SPLITS:
             raise ValueError("split must be 'route' or 'hop'")
-        if cost is None:
-            self.load(export)
-            if self._costs is not None:
-                self._costs = None
-                self.ctx.set_link_costs(None)
-        else:
-            self.set_link_costs(export, cost)
+        self._use_costs(export, cost)
         t = self._torch
         V, E = int(export.csr.V), int(export.csr.E)
         scen = normalise_scenarios(scenarios, E)
@@ -2029,40 +1989,27 @@ class RouteEngine(object):
         routed = np.zeros((nscen, n), bool)
         if n == 0 or nrows == 0 or nscen == 0 or V == 0:
             return load, lost, routed
-        if rows.min() < 0 or rows.max() >= nrows:
-            raise ValueError("failure_ecmp_link_loads: a pair names a row outside dsts")
-        order, off = _pairs_by_row(rows, nrows)
-        s = np.asarray(srcs, np.int64)[order]
-        s = np.where((s < 0) | (s >= V), -1, s).astype(np.int32)
+        order, off, s, w = _pairs_for_device(rows, nrows, srcs, V, weights,
+                                             "failure_ecmp_link_loads", "dsts")
         d = np.where((d < 0) | (d >= V), -1, d).astype(np.int32)
         soff = np.zeros(nscen + 1, np.int64)
         np.cumsum([a.shape[0] for a in scen], out=soff[1:])
         edges = np.concatenate(scen + [np.zeros(1, np.int32)]).astype(np.int32)
         d_dst = t.from_numpy(d).to(self.dev)
-        d_off = t.from_numpy(off).to(self.dev)
-        d_src = t.from_numpy(s).to(self.dev)
+        d_off, d_src, d_w = self._upload_pairs(off, s, w)
         d_soff = t.from_numpy(soff).to(self.dev)
         d_edges = t.from_numpy(edges).to(self.dev)
-        d_w = None
-        if weights is not None:
-            w = np.ascontiguousarray(np.asarray(weights, np.uint64)[order])
-            d_w = t.from_numpy(w.view(np.int64)).to(self.dev)
         d_load = t.zeros((nscen, max(E, 1)), dtype=t.float64, device=self.dev)
         d_lost = t.zeros(nscen, dtype=t.float64, device=self.dev)
         d_routed = t.zeros((nscen, n), dtype=t.uint8, device=self.dev)
         self._ready()
         self.ctx.failure_ecmp_link_loads_device(
-            d_dst.data_ptr(), nrows, d_off.data_ptr(), d_src.data_ptr(),
-            d_w.data_ptr() if d_w is not None else 0, nscen, d_soff.data_ptr(),
-            d_edges.data_ptr(), d_load.data_ptr(), d_lost.data_ptr(), d_routed.data_ptr(),
-            hop=split == "hop", timing=timing)
+            d_dst.data_ptr(), nrows, d_off.data_ptr(), d_src.data_ptr(), _ptr(d_w), nscen,
+            d_soff.data_ptr(), d_edges.data_ptr(), d_load.data_ptr(), d_lost.data_ptr(),
+            d_routed.data_ptr(), hop=split == "hop", timing=timing)
         self.ctx.synchronize()              # raises on a bad scenario list
         load = d_load[:, :E].cpu().numpy()
-        got = d_routed.cpu().numpy().astype(bool)
-        if isinstance(order, slice):
-            routed = got
-        else:
-            routed[:, order] = got
+        routed = _unsorted(d_routed.cpu().numpy().astype(bool), order)
         return load, d_lost.cpu().numpy(), routed
 
     def whatif_ecmp_link_loads(self, export, cost, dsts, rows, srcs, weights=None, scenarios=(),
@@ -2094,13 +2041,7 @@ class RouteEngine(object):
         bit-reproducible."""
         if split not in SPLITS:
             raise ValueError("split must be 'route' or 'hop'")
-        if cost is None:
-            self.load(export)
-            if self._costs is not None:
-                self._costs = None
-                self.ctx.set_link_costs(None)
-        else:
-            self.set_link_costs(export, cost)
+        self._use_costs(export, cost)
         t = self._torch
         V, E = int(export.csr.V), int(export.csr.E)
         scen = normalise_cost_scenarios(scenarios, export.csr)
@@ -2117,21 +2058,12 @@ class RouteEngine(object):
         peak_edge = np.full(nscen, -1, np.int32)
         if n == 0 or nrows == 0 or nscen == 0 or V == 0:
             return load, lost, routed, peak, peak_edge
-        if rows.min() < 0 or rows.max() >= nrows:
-            raise ValueError("whatif_ecmp_link_loads: a pair names a row outside dsts")
-        order, off = _pairs_by_row(rows, nrows)
-        s = np.asarray(srcs, np.int64)[order]
-        s = np.where((s < 0) | (s >= V), -1, s).astype(np.int32)
+        order, off, s, w = _pairs_for_device(rows, nrows, srcs, V, weights,
+                                             "whatif_ecmp_link_loads", "dsts")
         d = np.where((d < 0) | (d >= V), -1, d).astype(np.int32)
         d_dst = t.from_numpy(d).to(self.dev)
-        d_off = t.from_numpy(off).to(self.dev)
-        d_src = t.from_numpy(s).to(self.dev)
-        d_w = d_cap = None
-        if weights is not None:
-            w = np.ascontiguousarray(np.asarray(weights, np.uint64)[order])
-            d_w = t.from_numpy(w.view(np.int64)).to(self.dev)
-        if cap is not None:
-            d_cap = t.from_numpy(cap).to(self.dev)
+        d_off, d_src, d_w = self._upload_pairs(off, s, w)
+        d_cap = None if cap is None else t.from_numpy(cap).to(self.dev)
         budget = DEFAULT_TABLE_BUDGET if table_budget is None else int(table_budget)
         step = min(nscen, max(1, budget // max(1, 8 * E + n)))
         d_load = t.empty((step, max(E, 1)), dtype=t.float64, device=self.dev)
@@ -2140,7 +2072,6 @@ class RouteEngine(object):
             else None
         d_peak = t.empty(step, dtype=t.float64, device=self.dev)
         d_pedge = t.empty(step, dtype=t.int32, device=self.dev)
-        ptr = lambda a: a.data_ptr() if a is not None else 0     # noqa: E731
         self._ready()
         for c0 in range(0, nscen, step):
             part = scen[c0:c0 + step]
@@ -2158,9 +2089,9 @@ class RouteEngine(object):
             if d_routed is not None:
                 d_routed.zero_()
             self.ctx.whatif_ecmp_link_loads_device(
-                d_dst.data_ptr(), nrows, d_off.data_ptr(), d_src.data_ptr(), ptr(d_w), m,
+                d_dst.data_ptr(), nrows, d_off.data_ptr(), d_src.data_ptr(), _ptr(d_w), m,
                 d_soff.data_ptr(), d_edges.data_ptr(), d_costs.data_ptr(), d_load.data_ptr(),
-                ptr(d_lost), ptr(d_routed), ptr(d_cap), d_peak.data_ptr(), d_pedge.data_ptr(),
+                _ptr(d_lost), _ptr(d_routed), _ptr(d_cap), d_peak.data_ptr(), d_pedge.data_ptr(),
                 hop=split == "hop", timing=timing)
             self.ctx.synchronize()          # raises on a bad override list or capacity
             peak[c0:c0 + m] = d_peak[:m].cpu().numpy()
@@ -2170,11 +2101,7 @@ class RouteEngine(object):
             if loads:
                 load[c0:c0 + m] = d_load[:m, :E].cpu().numpy()
             if routed is not None:
-                got = d_routed[:m].cpu().numpy().astype(bool)
-                if isinstance(order, slice):
-                    routed[c0:c0 + m] = got
-                else:
-                    routed[c0:c0 + m][:, order] = got
+                routed[c0:c0 + m] = _unsorted(d_routed[:m].cpu().numpy().astype(bool), order)
         return load, lost, routed, peak, peak_edge
 
     def lfa_tables(self, export, cost, pcost_all, dsts, link_only=False, timing=False):
@@ -2189,21 +2116,13 @@ class RouteEngine(object):
         (int32 holding u32, as ``cost_tables`` returns it) or a numpy array,
         which is uploaded.  ``link_only``: SDNR_LFA_LINK_ONLY.  A destination
         outside [0, V) gives an empty row.  V above ``LFA_MAX_V`` raises."""
-        if cost is None:
-            self.load(export)
-            if self._costs is not None:
-                self._costs = None
-                self.ctx.set_link_costs(None)
-        else:
-            self.set_link_costs(export, cost)
+        self._use_costs(export, cost)
         t = self._torch
         V = int(export.csr.V)
         d = np.asarray(dsts, np.int64)
         D = int(d.shape[0])
         d = np.where((d < 0) | (d >= V), -1, d).astype(np.int32)
-        if _is_np(pcost_all):
-            pcost_all = t.from_numpy(np.ascontiguousarray(_pcost_u32(pcost_all)).view(np.int32)
-                                     ).to(self.dev)
+        pcost_all = self._pcost_device(pcost_all)
         if tuple(pcost_all.shape) != (V, V) or pcost_all.element_size() != 4:
             raise ValueError("pcost_all is the [V, V] 4-byte all-pairs table (row v: "
                              "destination v)")
@@ -2234,22 +2153,14 @@ class RouteEngine(object):
         ``cost_tables`` returns it) or a numpy array, which is uploaded;
         ``util``: uint32 [E] link utilisations in [0, UTIL_MAX].  A destination
         outside [0, V) gives an empty row."""
-        if cost is None:
-            self.load(export)
-            if self._costs is not None:
-                self._costs = None
-                self.ctx.set_link_costs(None)
-        else:
-            self.set_link_costs(export, cost)
+        self._use_costs(export, cost)
         t = self._torch
         V = int(export.csr.V)
         util = check_link_utilisation(export.csr, util)
         d = np.asarray(dsts, np.int64)
         D = int(d.shape[0])
         d = np.where((d < 0) | (d >= V), -1, d).astype(np.int32)
-        if _is_np(pcost):
-            pcost = t.from_numpy(np.ascontiguousarray(_pcost_u32(pcost)).view(np.int32)
-                                 ).to(self.dev)
+        pcost = self._pcost_device(pcost)
         if tuple(pcost.shape) != (D, V) or pcost.element_size() != 4:
             raise ValueError("pcost holds one 4-byte [V] row per destination")
         pcost = pcost.contiguous()

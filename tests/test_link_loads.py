@@ -281,3 +281,46 @@ def test_null_context_is_einval():
     assert L.sdnr_link_loads(None, None, 0, 0, None, None, None, None, _native.DEVICE_PTRS) == -22
     assert b"null context" in L.sdnr_last_error()
     assert _native.LOADS_TO_ROOT == 0x8
+
+
+def test_pairs_for_device_orders_clamps_and_names_the_caller():
+    """_pairs_for_device, the marshalling every pair-list engine call shares:
+    a stable order by row, the offsets, vertices outside [0, V) at -1, the
+    weights in the same order."""
+    V, nrows = 5, 4
+    rows = np.array([2, 0, 3, 0, 2], np.int64)                    # unsorted; row 1 has no pairs
+    verts = np.array([4, -1, V, 0, 3], np.int64)                  # -1 and V are no vertices
+    w = np.array([10, 20, 30, 40, U64], np.uint64)
+    order, off, x, wo = EN._pairs_for_device(rows, nrows, verts, V, w, "link_loads")
+    assert order.tolist() == [1, 3, 0, 4, 2]                      # stable within a row
+    assert off.dtype == np.int64 and off.tolist() == [0, 2, 2, 4, 5]
+    assert x.dtype == np.int32 and x.tolist() == [-1, 0, 4, 3, -1]
+    assert wo.dtype == np.uint64 and wo.flags.c_contiguous
+    assert wo.tolist() == [20, 40, 10, U64, 30]
+    got = np.array([7, 8, 9, 10, 11])                             # results in device order
+    assert EN._unsorted(got, order).tolist() == [9, 7, 11, 8, 10]
+    assert EN._unsorted(np.stack([got, got + 10]), order).tolist() == \
+        [[9, 7, 11, 8, 10], [19, 17, 21, 18, 20]]
+
+    # no weights: every pair weighs 1 on the device
+    assert EN._pairs_for_device(rows, nrows, verts, V, None, "link_loads")[3] is None
+
+    # rows already grouped: nothing is permuted
+    srt = np.array([0, 0, 2, 3], np.int64)
+    order, off, x, wo = EN._pairs_for_device(srt, nrows, [1, 2, 3, 4], V, [1, 2, 3, 4], "f")
+    assert isinstance(order, slice) and off.tolist() == [0, 2, 2, 3, 4]
+    assert x.tolist() == [1, 2, 3, 4] and wo.tolist() == [1, 2, 3, 4]
+    assert EN._unsorted(got, order) is got
+
+    # an empty list
+    order, off, x, wo = EN._pairs_for_device(np.zeros(0, np.int64), nrows, [], V, None, "f")
+    assert isinstance(order, slice) and off.tolist() == [0] * (nrows + 1)
+    assert x.dtype == np.int32 and x.shape == (0,) and wo is None
+
+    # a row index outside [0, nrows) raises in the caller's name
+    with pytest.raises(ValueError,
+                       match=r"^ecmp_link_loads: a pair names a row outside the table$"):
+        EN._pairs_for_device([0, nrows], nrows, [0, 0], V, None, "ecmp_link_loads")
+    with pytest.raises(ValueError,
+                       match=r"^whatif_ecmp_link_loads: a pair names a row outside dsts$"):
+        EN._pairs_for_device([-1], nrows, [0], V, None, "whatif_ecmp_link_loads", "dsts")
