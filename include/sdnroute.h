@@ -674,6 +674,90 @@ int sdnr_lfa_tables(sdnr_ctx *ctx, const uint32_t *pcost_all, const int32_t *dst
                     int32_t *backup, int32_t *backup_port, uint8_t *kind, uint32_t *counts,
                     uint32_t flags);
 
+/* Fast-reroute what-if: the link loads of a demand while the switches' backup
+ * next hops are forwarding -- after a failure, before the controller has
+ * re-routed (sdnr_failure_ecmp_link_loads is the state after that).  Integer
+ * and bit-exact.  Per (scenario k, destination row r), toward d = dst[r]:
+ *   a switch x with nh[r][x] == -1 forwards nowhere, and so does d itself (its
+ *   own two entries are not read);
+ *   fwd(x) = nh[r][x] if the link x -> nh[r][x] is not in scenario k;
+ *   else fwd(x) = backup[r][x] if that is not -1 and the link x -> backup[r][x]
+ *   is not in the scenario either: a REPAIR;
+ *   else x DROPS.
+ * A pair (s, d) follows fwd from s.  Its status is
+ *   0  no base route (following nh alone from s does not end at d), or s
+ *      outside [0, V);
+ *   1  delivered over primaries only (s == d included: it uses no link);
+ *   2  delivered through at least one repair;
+ *   3  dropped: the walk ends at a switch other than d;
+ *   4  looped: the walk never ends.
+ * Only DELIVERED pairs (status 1 or 2) add load: their weight on every link of
+ * their walk.  A pair that is dropped or loops adds nothing to any link, as a
+ * pair without a route adds nothing in sdnr_failure_ecmp_link_loads.
+ *   dst        [nrows] the destination (dense id) of row r;
+ *   nh, backup [nrows][V] int32: the rows sdnr_cost_tables (or
+ *              sdnr_shortest_tables) and sdnr_lfa_tables write for dst, -1: none.
+ *              They are taken as given: a backup need not be a loop-free
+ *              alternate, and one that leads into a cycle gives status 4;
+ *   pair_off, srcs, weight: as in sdnr_cost_ecmp_link_loads; pair i below is
+ *              srcs[pair_off[0] + i], npairs = pair_off[nrows] - pair_off[0];
+ *   nscen, scen_off, scen_edges: as in sdnr_failure_ecmp_link_loads -- CSR
+ *              edge indices in [0, E), ascending within a scenario, duplicates
+ *              allowed, directed;
+ *   load       [nscen][E] u64.  The call ADDS (sums wrap: the order of the
+ *              atomics does not matter);
+ *   stat       [nscen][4] u64 or NULL.  The call ADDS the weight of the pairs
+ *              of status 2 (repaired), 3 (dropped), 4 (looped) and 0 (no base
+ *              route), in this order;
+ *   status     [nscen][npairs] u8 or NULL, WRITTEN for the pairs of every row
+ *              that has pairs;
+ *   peak       [nscen] u64, WRITTEN: the largest load[k][e], over load as it
+ *              stands after this call's additions;
+ *   peak_edge  [nscen] int32, WRITTEN: the smallest e that attains peak[k], -1
+ *              when peak[k] is 0.  Both are given or both are NULL.
+ * Defining property: slice k equals sdnr_link_loads with SDNR_LOADS_TO_ROOT
+ * over the rows fwd of scenario k and the delivered pairs.  An empty scenario
+ * gives the loads of nh itself with every routed pair at status 1.
+ * The loads of the rows without any failure are computed once per call and
+ * added to every slice; then only the AFFECTED items are recomputed -- (k, r)
+ * where row r has pairs and some link x -> n of scenario k has nh[r][x] == n --
+ * one workgroup each with the row's state in LDS (26 bytes per vertex).
+ * sdnr_last_frr_items reports their number.  There is no other form: V is at
+ * most kFrrMaxV = 6,200 (the fat-tree k=48, the dragonfly a16 h8 p8 and the
+ * 16^3 torus fit), above it SDNR_ERR_INVAL before anything is read.  The call
+ * keeps one u64 per (row, vertex), 8 bytes per item and 12 per scenario entry
+ * in the context scratch: more than 1 GiB is SDNR_ERR_NOMEM (split the
+ * scenarios).
+ * Device pointers only (flags must hold SDNR_DEVICE_PTRS); asynchronous on the
+ * context stream (the ends of pair_off and scen_off are read back first: not
+ * monotone is SDNR_ERR_INVAL); on a multi-device context it runs on the
+ * primary device; SDNR_TIMING times the item kernel, which sdnr_last_kernel
+ * names (not the base, the pre-pass or the peak reduction); sdnr_last_launches
+ * is 1.  Without an uploaded graph: SDNR_ERR_STATE.  Negative counts, NULL
+ * where a buffer is required, one of peak / peak_edge without the other:
+ * SDNR_ERR_INVAL.  nscen == 0: SDNR_OK, nothing touched.  nrows == 0 or no
+ * pairs: nothing is added; peak and peak_edge are still written from load as it
+ * stands.  A destination outside [0, V) is an empty row: nothing added, its
+ * pairs at status 0.
+ * Reported by sdnr_synchronize as SDNR_ERR_INVAL, the other rows, scenarios
+ * and items unaffected and the context usable:
+ *   an nh row that is no in-tree of the graph (an entry >= V or equal to its
+ *   own vertex, a cycle, a link the graph lacks under a vertex that carries
+ *   demand) or whose pair_off lies outside the pair list: the row adds nothing
+ *   to any slice or stat and its pairs read status 0;
+ *   a backup in use that is < -1, >= V or no out-neighbour: that item adds
+ *   nothing of its own -- the slice keeps the row's base loads and statuses;
+ *   a failed-link index outside [0, E): that entry is ignored;
+ *   a scenario that is not ascending or whose scen_off lies outside the list:
+ *   it is taken as empty.
+ * A forwarding loop that backup causes is data, not an error. */
+int sdnr_frr_link_loads(sdnr_ctx *ctx, const int32_t *dst, const int32_t *nh,
+                        const int32_t *backup, int32_t nrows, const int64_t *pair_off,
+                        const int32_t *srcs, const uint64_t *weight, int32_t nscen,
+                        const int64_t *scen_off, const int32_t *scen_edges, uint64_t *load,
+                        uint64_t *stat, uint8_t *status, uint64_t *peak, int32_t *peak_edge,
+                        uint32_t flags);
+
 /* Least-loaded routes: per destination, inside the least-cost (ECMP) set, the
  * route whose busiest link is the least busy -- the controller's question
  * "given what the links carry now, which of the equal-cost routes should this
@@ -884,7 +968,8 @@ int sdnr_last_launches(const sdnr_ctx *ctx, int32_t *launches);
  * kernels of sdnr_link_loads, sdnr_ecmp_link_loads, sdnr_cost_ecmp_link_loads,
  * sdnr_cost_tables, sdnr_widest_tables, sdnr_failure_ecmp_link_loads,
  * sdnr_whatif_ecmp_link_loads, sdnr_lfa_tables, sdnr_fair_rates,
- * sdnr_ecmp_fair_rates (their row kernel), sdnr_multicast_trees and
+ * sdnr_ecmp_fair_rates (their row kernel), sdnr_multicast_trees,
+ * sdnr_frr_link_loads (its item kernel, over the affected items) and
  * sdnr_ecmp_counts give every workgroup the rows (batches, items, groups) r,
  * r + grid, r + 2 * grid, ...: with more units of work than this a workgroup
  * takes more than one.  The other entry points leave it as it was (0 before
@@ -895,6 +980,11 @@ int sdnr_last_grid(const sdnr_ctx *ctx, int64_t *workgroups);
  * batch size, or, when the call folded twin classes, one per class present
  * in the batch -- the other rows were derived (0 before the first call). */
 int sdnr_last_dfs_searched(sdnr_ctx *ctx, int32_t *n);
+
+/* (Scenario, row) items the last sdnr_frr_link_loads call recomputed (waits
+ * for that call): the affected items, each once; 0 when the call had nothing
+ * to do, and before the first call. */
+int sdnr_last_frr_items(sdnr_ctx *ctx, int64_t *items);
 
 /* Form of the search kernel in the last sdnr_dfs_tables* call: 0 the
  * full-load form, 1 the low-load form -- a folded call whose previous call on

@@ -86,6 +86,12 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "positive finite number (that link skipped), pair_off or scen_off "
                              "outside their lists, relaxation sweeps that outran V or a route "
                              "count above the double range: loads invalid");
+        if (h & kErrFrrLoads)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_frr_link_loads: an nh row that is no in-tree "
+                             "of the uploaded graph (that row adds nothing), a backup that is no "
+                             "out-neighbour (that item keeps the base loads), a failed-link index "
+                             "outside [0, E) (ignored), a scenario that is not ascending (taken "
+                             "as empty), pair_off or scen_off outside their lists: loads invalid");
         if (h & kErrLfa)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_lfa_tables: a requested row of pcost_all is "
                              "not a least-cost labelling of the uploaded graph under the costs in "
@@ -431,6 +437,7 @@ int sdnr_destroy(sdnr_ctx *ctx)
     if (ctx->h_flag) (void)hipHostFree(ctx->h_flag);
     if (ctx->h_pub) (void)hipHostFree(ctx->h_pub);
     if (ctx->h_live) (void)hipHostFree(ctx->h_live);
+    if (ctx->h_frr_items) (void)hipHostFree(ctx->h_frr_items);
     if (ctx->ev_flag) (void)hipEventDestroy(ctx->ev_flag);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -1747,6 +1754,61 @@ int sdnr_whatif_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *dst, int32_t nrows
     }
     // the reduction is over load as it stands now: the call ADDED into it
     if (peak) return sdnr_launch_whatif_peak(ctx, nscen, load, capacity, peak, peak_edge);
+    return SDNR_OK;
+}
+
+int sdnr_frr_link_loads(sdnr_ctx *ctx, const int32_t *dst, const int32_t *nh,
+                        const int32_t *backup, int32_t nrows, const int64_t *pair_off,
+                        const int32_t *srcs, const uint64_t *weight, int32_t nscen,
+                        const int64_t *scen_off, const int32_t *scen_edges, uint64_t *load,
+                        uint64_t *stat, uint8_t *status, uint64_t *peak, int32_t *peak_edge,
+                        uint32_t flags)
+{
+    static const char name[] = "sdnr_frr_link_loads";
+    CHECK_CTX(ctx);
+    int rc = open_pair_call(ctx, flags, nrows < 0 || nscen < 0, name);
+    if (rc) return rc;
+    if (ctx->V > kFrrMaxV)
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: V = %d above the LDS form's %d vertices", name,
+                         ctx->V, kFrrMaxV);
+    if ((peak == nullptr) != (peak_edge == nullptr))
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: peak and peak_edge are both given or both NULL",
+                         name);
+    ctx->frr_items_pending = false;
+    if (nscen == 0) return SDNR_OK;
+    if (!load || (nrows > 0 && (!dst || !pair_off || !scen_off)))
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
+    SDNR_HIP(hipSetDevice(ctx->device));
+    if (nrows > 0) {
+        // the bounds of the pair list and of the failed-link list
+        int64_t lo, hi, flo, fhi;
+        bool empty;
+        if ((rc = list_bounds(ctx, pair_off, nrows, name, "pair_off", &lo, &hi, &empty))) return rc;
+        if ((rc = list_bounds(ctx, scen_off, nscen, name, "scen_off", &flo, &fhi))) return rc;
+        if (!empty && ctx->V > 0) {
+            if (!srcs || !nh || !backup || (fhi > flo && !scen_edges))
+                return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
+            ctx->timed = (flags & SDNR_TIMING) != 0;
+            rc = sdnr_launch_frr_link_loads(ctx, dst, nh, backup, nrows, pair_off, lo, hi, srcs,
+                                            weight, nscen, scen_off, flo, fhi, scen_edges, load,
+                                            stat, status);
+            if (rc) return rc;
+        }
+    }
+    // the reduction is over load as it stands now: the call ADDED into it
+    if (peak) return sdnr_launch_frr_peak(ctx, nscen, load, peak, peak_edge);
+    return SDNR_OK;
+}
+
+int sdnr_last_frr_items(sdnr_ctx *ctx, int64_t *items)
+{
+    CHECK_CTX(ctx);
+    if (!items) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_last_frr_items: null out");
+    *items = 0;
+    if (!ctx->frr_items_pending) return SDNR_OK;
+    SDNR_HIP(hipSetDevice(ctx->device));
+    SDNR_HIP(hipStreamSynchronize(ctx->stream));
+    *items = *ctx->h_frr_items;
     return SDNR_OK;
 }
 

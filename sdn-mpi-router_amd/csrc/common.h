@@ -227,6 +227,10 @@ struct sdnr_ctx {
     int64_t last_grid = 0;              // workgroups of the last row-persistent launch (sdnr_last_grid)
     int32_t last_sweeps = 0;            // Bellman-Ford sweeps of the last APSP call
     int32_t plane_depth = 0;            // levels the bit-plane BFS last needed on this graph
+    // sdnr_frr_link_loads: the affected-item count of the last call, copied
+    // into a pinned host word behind its kernels (sdnr_last_frr_items)
+    int64_t *h_frr_items = nullptr;
+    bool frr_items_pending = false;     // the last call launched: the word is (or will be) its count
     int *d_err = nullptr;               // kernel watchdog word (0 = ok)
     int *h_flag = nullptr;              // pinned host words for level-loop checks
     int *h_pub = nullptr;               // coherent host words a kernel publishes into
@@ -378,6 +382,17 @@ constexpr size_t kMcastLdsBytes = 32 * 1024;
 static_assert(4 * kMcastLdsBytes + 4 * 1024 <= SDNR_LDS_PER_CU,
               "four workgroups' maps and their static words fit the CU's LDS");
 
+constexpr int kErrFrrLoads = 8388608; // sdnr_frr_link_loads: a row that is no in-tree / a next hop or backup that is no out-neighbour / a bad scenario list / bad offsets
+
+// sdnr_frr_link_loads keeps an item's doubling generations (two u64, two u16),
+// its classification word (u32) and its patched next hop (u16) in LDS: 26
+// bytes per vertex, up to this V -- what the CU's LDS holds beside the kernel's
+// static words (the barrier votes, under 512 bytes), rounded down to a hundred:
+// 6,200, 161,200 of 163,840 bytes.  There is no global-scratch form.
+constexpr int kFrrBytesPerV = 26;
+constexpr int kFrrMaxV = (SDNR_LDS_PER_CU - 512) / kFrrBytesPerV / 100 * 100;
+static_assert(kFrrMaxV == 6200 && kFrrMaxV < 0xFFFF, "next hops in LDS are u16");
+
 // error plumbing (capi.hip)
 int sdnr_fail(int code, const char *fmt, ...);
 int sdnr_hip_fail(hipError_t e, const char *what);
@@ -478,6 +493,17 @@ int sdnr_launch_whatif_ecmp_link_loads(sdnr_ctx *ctx, const int32_t *d_dst, int3
                                        int64_t scen_hi, const int32_t *d_scen_edges,
                                        const uint32_t *d_scen_costs, double *d_load,
                                        double *d_lost, uint8_t *d_routed, bool hop);
+// fast-reroute what-if loads: LFA repair active, per failure scenario (frr_loads.hip),
+// and the largest entry of every [E] slice of a u64 load plane
+int sdnr_launch_frr_link_loads(sdnr_ctx *ctx, const int32_t *d_dst, const int32_t *d_nh,
+                               const int32_t *d_backup, int32_t nrows, const int64_t *d_pair_off,
+                               int64_t pair_lo, int64_t pair_hi, const int32_t *d_srcs,
+                               const uint64_t *d_weight, int32_t nscen,
+                               const int64_t *d_scen_off, int64_t scen_lo, int64_t scen_hi,
+                               const int32_t *d_scen_edges, uint64_t *d_load, uint64_t *d_stat,
+                               uint8_t *d_status);
+int sdnr_launch_frr_peak(sdnr_ctx *ctx, int32_t nscen, const uint64_t *d_load, uint64_t *d_peak,
+                         int32_t *d_peak_edge);
 int sdnr_launch_whatif_peak(sdnr_ctx *ctx, int32_t nscen, const double *d_load,
                             const double *d_capacity, double *d_peak, int32_t *d_peak_edge);
 // loop-free alternate next hops per destination (lfa_tables.hip)

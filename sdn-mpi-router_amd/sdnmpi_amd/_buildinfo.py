@@ -22,7 +22,8 @@ INCLUDE = os.path.join(os.path.dirname(PKG), "include")
 SOURCES = ("capi.hip", "dfs.hip", "shortest.hip", "apsp.hip", "routes.hip", "ecmp.hip",
            "incremental.hip", "loads.hip", "ecmp_loads.hip", "cost_tables.hip",
            "cost_ecmp_loads.hip", "failure_loads.hip", "lfa_tables.hip", "whatif_loads.hip",
-           "widest_tables.hip", "fair_rates.hip", "ecmp_fair_rates.hip", "multicast.hip")
+           "widest_tables.hip", "fair_rates.hip", "ecmp_fair_rates.hip", "multicast.hip",
+           "frr_loads.hip")
 HEADERS = (("csrc", "common.h"), ("csrc", "rowstate.h"), ("csrc", "scenario_row.h"),
            ("include", "sdnroute.h"))
 FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function")

@@ -54,7 +54,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_last_dfs_form", "sdnr_last_dfs_quotient",
     "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables", "sdnr_whatif_ecmp_link_loads",
     "sdnr_widest_tables", "sdnr_fair_rates", "sdnr_ecmp_fair_rates", "sdnr_multicast_trees",
-    "sdnr_last_grid",
+    "sdnr_last_grid", "sdnr_frr_link_loads", "sdnr_last_frr_items",
 )
 
 
@@ -132,6 +132,9 @@ def _bind(L):
         "sdnr_last_dfs_searched": ([vp, ctypes.POINTER(i32)], c_int),
         "sdnr_last_dfs_form": ([vp, ctypes.POINTER(i32)], c_int),
         "sdnr_last_dfs_quotient": ([vp, ctypes.POINTER(i32)], c_int),
+        "sdnr_frr_link_loads": ([vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp,
+                                 u32], c_int),
+        "sdnr_last_frr_items": ([vp, ctypes.POINTER(ctypes.c_int64)], c_int),
     }
     # an A/B build named by SDNROUTE_LIB may predate some entry points: those
     # stay unbound (calling one raises AttributeError); the in-tree library
@@ -589,6 +592,26 @@ class Context(object):
             int(nscen), _p(scen_off_ptr), _p(scen_edges_ptr), _p(scen_costs_ptr), _p(load_ptr),
             _p(lost_ptr), _p(routed_ptr), _p(capacity_ptr), _p(peak_ptr), _p(peak_edge_ptr), flags))
 
+    def frr_link_loads_device(self, dst_ptr, nh_ptr, backup_ptr, nrows, pair_off_ptr, srcs_ptr,
+                              weight_ptr, nscen, scen_off_ptr, scen_edges_ptr, load_ptr,
+                              stat_ptr=0, status_ptr=0, peak_ptr=0, peak_edge_ptr=0, timing=False):
+        """Add the link loads of a demand while the backup next hops forward,
+        once per failure scenario, into ``load`` (u64 [nscen][E]; the caller
+        zeroes it): row r forwards toward ``dst[r]`` over ``nh`` (int32
+        [nrows][V]) and, where the scenario took the primary link, over
+        ``backup`` (the same shape); scenarios as in
+        ``failure_ecmp_link_loads_device``.  ``stat`` (u64 [nscen][4], added
+        into: the weight repaired, dropped, looped, without a base route),
+        ``status`` (u8 [nscen][npairs], written: 0 no base route, 1 primary,
+        2 repaired, 3 dropped, 4 looped) and ``peak`` / ``peak_edge`` (u64 /
+        int32 [nscen], written, both or neither) may be 0:
+        sdnr_frr_link_loads, device pointers, asynchronous."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0)
+        _check(self._lib.sdnr_frr_link_loads(
+            self._h, _p(dst_ptr), _p(nh_ptr), _p(backup_ptr), int(nrows), _p(pair_off_ptr),
+            _p(srcs_ptr), _p(weight_ptr), int(nscen), _p(scen_off_ptr), _p(scen_edges_ptr),
+            _p(load_ptr), _p(stat_ptr), _p(status_ptr), _p(peak_ptr), _p(peak_edge_ptr), flags))
+
     def lfa_tables_device(self, pcost_all_ptr, dst_ptr, ndst, backup_ptr, backup_port_ptr,
                           kind_ptr, counts_ptr=0, link_only=False, timing=False):
         """Loop-free alternate next hops of ``ndst`` destinations
@@ -745,6 +768,13 @@ class Context(object):
         rep = np.empty(max(self.V, 0), np.int32)
         _check(self._lib.sdnr_graph_twin_reps(self._h, _ptr(rep)))
         return rep
+
+    def last_frr_items(self):
+        """(Scenario, row) items the last ``frr_link_loads_device`` call
+        recomputed -- the affected ones (sdnr_last_frr_items; waits)."""
+        n = ctypes.c_int64(0)
+        _check(self._lib.sdnr_last_frr_items(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def last_dfs_searched(self):
         """Sources the last DFS table call searched: fewer than the batch when

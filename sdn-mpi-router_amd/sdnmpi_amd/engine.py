@@ -47,6 +47,7 @@ __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "COST_ECMP_LDS_MAX_V", "FAILURE_LDS_MAX_V", "normalise_scenarios",
            "failure_ecmp_link_loads_host", "normalise_cost_scenarios",
            "whatif_ecmp_link_loads_host", "peak_utilisation", "lfa_tables_host", "LFA_MAX_V", "LFA_BACKUP",
+           "frr_link_loads_host", "FRR_MAX_V",
            "LFA_DOWNSTREAM", "LFA_NODE", "widest_tables_host", "check_link_utilisation", "UTIL_MAX",
            "WIDEST_LDS_MAX_V", "WIDEST_LDS_B4_MAX_V", "WIDEST_LDS_B6_MAX_V", "fair_rates_host",
            "check_fair_flows", "FAIR_LDS_MAX_V", "FAIR_MULT_LIMIT", "ecmp_fair_rates_host",
@@ -1379,6 +1380,150 @@ def lfa_tables_host(csr, cost, pcost_all, dsts, link_only=False):
     return backup, bport, kind, counts
 
 
+FRR_MAX_V = 6200                # csrc/common.h kFrrMaxV: the fast-reroute item state in LDS
+
+
+def frr_link_loads_host(csr, nh, backup, dsts, rows, srcs, weights=None, scenarios=()):
+    """numpy restatement of sdnr_frr_link_loads (the CPU tests' engine double
+    and an independent check of frr_loads.hip): ``(load uint64 [nscen, E], stat
+    uint64 [nscen, 4], status uint8 [nscen, npairs], peak uint64 [nscen],
+    peak_edge int32 [nscen], items)`` of pairs (toward dense switch
+    ``dsts[rows[i]]``, from ``srcs[i]``, weight ``weights[i]`` or 1) forwarded
+    over the next-hop rows ``nh`` and, where a scenario took a switch's primary
+    link, over ``backup`` (int32 [nrows, V] each, -1: none), once per scenario of
+    ``scenarios`` (int arrays of failed CSR edge indices).
+
+    ``status``: 0 no base route (or a source or destination that is no
+    vertex), 1 delivered over primaries, 2 delivered through a repair, 3
+    dropped, 4 looped; only delivered pairs add load.  ``stat[k]``: the weight
+    repaired, dropped, looped, without a base route.  ``items``: the (scenario,
+    row) items some failed link x -> n touches (``nh[r, x] == n``, the row has
+    pairs).
+
+    Per item the row is patched (``fwd``), every vertex is classified by the
+    2^t-th successor under ``fwd`` with the switches that forward nowhere as
+    fixed points, and the delivered sources are summed over the patched row by
+    ``link_loads_host``; the unaffected rows of a scenario keep their base
+    loads.  u64 sums wrap, as on the device."""
+    V, E = int(csr.V), int(csr.E)
+    scen = normalise_scenarios(scenarios, E)
+    nscen = len(scen)
+    dsts = np.asarray(dsts, np.int64).reshape(-1)
+    rows = np.asarray(rows, np.int64).reshape(-1)
+    srcs = np.asarray(srcs, np.int64).reshape(-1)
+    n, nrows = int(rows.shape[0]), int(dsts.shape[0])
+    w = np.ones(n, np.uint64) if weights is None else np.asarray(weights, np.uint64).reshape(-1)
+    load = np.zeros((nscen, E), np.uint64)
+    stat = np.zeros((nscen, 4), np.uint64)
+    status = np.zeros((nscen, n), np.uint8)
+    peak = np.zeros(nscen, np.uint64)
+    peak_edge = np.full(nscen, -1, np.int32)
+    items = 0
+    if n and (rows.min() < 0 or rows.max() >= nrows):
+        raise ValueError("frr_link_loads_host: a pair names a row outside dsts")
+    if n and nscen and V:
+        nh = np.asarray(nh, np.int64).reshape(nrows, V)
+        backup = np.asarray(backup, np.int64).reshape(nrows, V)
+        if (nh >= V).any() or (backup >= V).any() or (backup < -1).any():
+            raise ValueError("frr_link_loads_host: a next hop that is no vertex")
+        keys, _ = _edge_keys_host(csr)
+        ids = np.arange(V, dtype=np.int64)
+        rounds = max(1, V).bit_length() + 1
+        s_ok = (srcs >= 0) & (srcs < V)
+        sc = np.where(s_ok, srcs, 0)
+        esrc = np.repeat(ids, np.diff(np.asarray(csr.row_ptr, np.int64)))
+        ecol = np.asarray(csr.col, np.int64)
+        by_row = [np.nonzero(rows == r)[0] for r in range(nrows)]
+        live = [r for r in range(nrows) if by_row[r].size and 0 <= dsts[r] < V]
+
+        def has_link(x, b):
+            k = x * V + b
+            e = np.minimum(np.searchsorted(keys, k), max(E - 1, 0))
+            return E > 0 and keys[e] == k
+
+        def classify(fwd, end, rep):
+            """(end kind, repaired) per vertex: end 0 where the walk has none."""
+            jump = np.where(end > 0, ids, fwd)
+            for _ in range(rounds):
+                rep = rep | rep[jump]
+                jump = jump[jump]
+            return end[jump], rep
+
+        def row_loads(r, fwd, good):
+            """[E] loads of the pairs ``good`` of row r over the parents fwd."""
+            if not good.size:
+                return np.zeros(E, np.uint64)
+            return link_loads_host(csr, fwd[None, :].astype(np.int32), INT32,
+                                   np.zeros(good.shape[0], np.int64), srcs[good], w[good],
+                                   to_root=True)
+
+        base_rows, base_ok = {}, {}
+        base = np.zeros(E, np.uint64)
+        gone = np.uint64(0)
+        for r in range(nrows):
+            mine = by_row[r]
+            if r not in live:
+                gone += w[mine].sum(dtype=np.uint64)
+                continue
+            d = int(dsts[r])
+            fwd = nh[r].copy()
+            fwd[d] = -1
+            if (fwd == ids).any():
+                raise ValueError("frr_link_loads_host: a next hop that is its own vertex")
+            end = np.where(ids == d, 1, np.where(fwd < 0, 2, 0))
+            got, _ = classify(fwd, end, np.zeros(V, bool))
+            if (got == 0).any():
+                raise ValueError("frr_link_loads_host: a next-hop row is not an in-tree")
+            ok = s_ok[mine] & (got[sc[mine]] == 1)
+            base_ok[r] = ok
+            base_rows[r] = row_loads(r, np.where(got == 1, fwd, -1), mine[ok])
+            base += base_rows[r]
+            gone += w[mine[~ok]].sum(dtype=np.uint64)
+            status[:, mine[ok]] = 1
+        load += base[None, :]
+        stat[:, 3] = gone
+        for k, failed in enumerate(scen):
+            fx, fn = esrc[failed], ecol[failed]
+            down = set((fx * V + fn).tolist())
+            for r in live:
+                d = int(dsts[r])
+                hit = np.nonzero((nh[r][fx] == fn) & (fx != d))[0]
+                if not hit.size:
+                    continue
+                items += 1
+                mine = by_row[r]
+                fwd = nh[r].copy()
+                fwd[d] = -1
+                end = np.where(ids == d, 1, np.where(fwd < 0, 2, 0))
+                rep = np.zeros(V, bool)
+                for x in np.unique(fx[hit]).tolist():
+                    b = int(backup[r, x])
+                    if b >= 0 and not has_link(x, b):
+                        raise ValueError("frr_link_loads_host: a backup that is no out-neighbour")
+                    if b < 0 or x * V + b in down:
+                        fwd[x], end[x] = -1, 3                 # drops
+                    elif b == x:
+                        fwd[x], end[x] = -1, 4                 # forwards to itself for ever
+                    else:
+                        fwd[x], rep[x] = b, True
+                got, rp = classify(fwd, end, rep)
+                ok = base_ok[r]
+                cls = got[sc[mine]]
+                st = np.where(cls == 1, np.where(rp[sc[mine]], 2, 1),
+                              np.where((cls == 2) | (cls == 3), 3, 4))
+                st = np.where(ok, st, 0).astype(np.uint8)
+                status[k, mine] = st
+                for j, code in enumerate((2, 3, 4)):
+                    stat[k, j] += w[mine[st == code]].sum(dtype=np.uint64)
+                good = mine[(st == 1) | (st == 2)]
+                load[k] += row_loads(r, np.where(got == 1, fwd, -1), good) - base_rows[r]
+    for k in range(nscen):
+        if E and load[k].max() > 0:
+            peak[k] = load[k].max()
+            peak_edge[k] = int(np.argmax(load[k]))
+    return load, stat, status, peak, peak_edge, items
+
+
 class RouteEngine(object):
     """The GPU route engine of one TopologyDB: HIP device ``device`` (int),
     or the devices of a list (single-process multi-GPU, sources sharded over
@@ -2139,6 +2284,96 @@ class RouteEngine(object):
                                        link_only=link_only, timing=timing)
             self.ctx.synchronize()          # raises on a row that is no least-cost labelling
         return backup, bport, kind, counts.cpu().numpy().view(np.uint32)
+
+    def frr_link_loads(self, export, nh, backup, dsts, rows, srcs, weights=None, scenarios=(),
+                       planes=True, timing=False, table_budget=None):
+        """Fast-reroute what-if (frr_loads.hip, sdnr_frr_link_loads): what the
+        links carry while the backup next hops forward, once per failure
+        scenario, nothing uploaded or cached changing: ``(load uint64 [nscen,
+        E], stat uint64 [nscen, 4], status uint8 [nscen, npairs], peak uint64
+        [nscen], peak_edge int32 [nscen], items)`` on the host, as
+        ``frr_link_loads_host`` defines them.
+
+        ``nh``, ``backup``: int32 [nrows, V] next-hop and backup rows toward
+        ``dsts`` (device tensors or numpy; ``cost_tables`` / ``lfa_tables``
+        write them); pair i goes from ``srcs[i]`` toward ``dsts[rows[i]]`` and
+        weighs ``weights[i]`` (u64, None: 1).  ``scenarios``: a list of int
+        arrays of failed CSR edge indices, sorted and deduplicated here.  The
+        scenarios are processed in chunks whose planes fit ``table_budget``
+        bytes (None: DEFAULT_TABLE_BUDGET), 8 E + npairs bytes per scenario, in
+        one device buffer reused across the chunks.  ``planes=False``: the load
+        planes never leave the device and no status is written; load and
+        status come back as None -- an N-1 sweep wants the numbers per
+        scenario.  ``items``: the (scenario, row) items the kernel recomputed.
+        Exact: u64 sums."""
+        self.load(export)
+        t = self._torch
+        V, E = int(export.csr.V), int(export.csr.E)
+        if V > FRR_MAX_V:
+            raise ValueError("frr_link_loads keeps a row in LDS: %d switches are above its %d"
+                             % (V, FRR_MAX_V))
+        scen = normalise_scenarios(scenarios, E)
+        nscen = len(scen)
+        rows = np.asarray(rows, np.int64)
+        n = int(rows.shape[0])
+        d = np.asarray(dsts, np.int64)
+        nrows = int(d.shape[0])
+        load = np.zeros((nscen, E), np.uint64) if planes else None
+        status = np.zeros((nscen, n), np.uint8) if planes else None
+        stat = np.zeros((nscen, 4), np.uint64)
+        peak = np.zeros(nscen, np.uint64)
+        peak_edge = np.full(nscen, -1, np.int32)
+        if n == 0 or nrows == 0 or nscen == 0 or V == 0:
+            return load, stat, status, peak, peak_edge, 0
+        order, off, s, w = _pairs_for_device(rows, nrows, srcs, V, weights, "frr_link_loads",
+                                             "dsts")
+        d = np.where((d < 0) | (d >= V), -1, d).astype(np.int32)
+
+        def table(a, what):
+            if _is_np(a):
+                a = t.from_numpy(np.ascontiguousarray(a, np.int32)).to(self.dev)
+            if tuple(a.shape) != (nrows, V) or a.dtype != t.int32:
+                raise ValueError("frr_link_loads: %s is int32 [%d, %d]" % (what, nrows, V))
+            return a.contiguous()
+
+        d_nh, d_bk = table(nh, "nh"), table(backup, "backup")
+        d_dst = t.from_numpy(d).to(self.dev)
+        d_off, d_src, d_w = self._upload_pairs(off, s, w)
+        budget = DEFAULT_TABLE_BUDGET if table_budget is None else int(table_budget)
+        step = min(nscen, max(1, budget // max(1, 8 * E + n)))
+        d_load = t.empty((step, max(E, 1)), dtype=t.int64, device=self.dev)
+        d_stat = t.empty((step, 4), dtype=t.int64, device=self.dev)
+        d_status = t.empty((step, n), dtype=t.uint8, device=self.dev) if planes else None
+        d_peak = t.empty(step, dtype=t.int64, device=self.dev)
+        d_pedge = t.empty(step, dtype=t.int32, device=self.dev)
+        items = 0
+        self._ready()
+        for c0 in range(0, nscen, step):
+            part = scen[c0:c0 + step]
+            m = len(part)
+            soff = np.zeros(m + 1, np.int64)
+            np.cumsum([a.shape[0] for a in part], out=soff[1:])
+            edges = np.concatenate(part + [np.zeros(1, np.int32)]).astype(np.int32)
+            d_soff = t.from_numpy(soff).to(self.dev)
+            d_edges = t.from_numpy(edges).to(self.dev)
+            d_load.zero_()
+            d_stat.zero_()
+            if d_status is not None:
+                d_status.zero_()
+            self.ctx.frr_link_loads_device(
+                d_dst.data_ptr(), d_nh.data_ptr(), d_bk.data_ptr(), nrows, d_off.data_ptr(),
+                d_src.data_ptr(), _ptr(d_w), m, d_soff.data_ptr(), d_edges.data_ptr(),
+                d_load.data_ptr(), d_stat.data_ptr(), _ptr(d_status), d_peak.data_ptr(),
+                d_pedge.data_ptr(), timing=timing)
+            self.ctx.synchronize()          # raises on a bad row, backup or scenario list
+            items += self.ctx.last_frr_items()
+            stat[c0:c0 + m] = d_stat[:m].cpu().numpy().view(np.uint64)
+            peak[c0:c0 + m] = d_peak[:m].cpu().numpy().view(np.uint64)
+            peak_edge[c0:c0 + m] = d_pedge[:m].cpu().numpy()
+            if planes:
+                load[c0:c0 + m] = d_load[:m, :E].cpu().numpy().view(np.uint64)
+                status[c0:c0 + m] = _unsorted(d_status[:m].cpu().numpy(), order)
+        return load, stat, status, peak, peak_edge, items
 
     def widest_tables(self, export, cost, pcost, util, dsts, timing=False):
         """Least-loaded tables inside the least-cost DAG (widest_tables.hip,

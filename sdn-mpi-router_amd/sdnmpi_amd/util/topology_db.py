@@ -38,7 +38,7 @@ try:   # the reference takes OFPP_LOCAL from Ryu's OpenFlow 1.0 module (:5)
 except Exception:   # noqa: BLE001 - Ryu is not a dependency of the engine
     OFPP_LOCAL = 0xfffe
 
-__all__ = ["TopologyDB", "LinkLoads", "SplitLinkLoads", "FailureLoads", "CostChangeLoads",
+__all__ = ["TopologyDB", "LinkLoads", "SplitLinkLoads", "FailureLoads", "CostChangeLoads", "FrrLoads",
            "CostTuning", "Admission", "FairRates", "MulticastTree", "OFPP_LOCAL",
            "sdn_mpi_mac"]
 
@@ -222,6 +222,48 @@ class CostChangeLoads(FailureLoads):
         self.peak = peak
         self.peak_link = peak_link
         self.base_peak = base_peak
+
+
+class FrrLoads(object):
+    """Predicted traffic per link while fast reroute is forwarding, under each
+    of a list of link-failure scenarios (:meth:`TopologyDB.frr_link_loads`).
+
+    ``scenarios``: as in :class:`FailureLoads`.  ``load``: uint64 [nscen, E],
+    row k the exact link loads of scenario k in the order of
+    :class:`LinkLoads`' records, None when the planes were not asked for.  Per
+    scenario, uint64 [nscen]: ``repaired`` -- the weight delivered through at
+    least one backup next hop --, ``dropped`` -- the weight that reached a
+    switch whose primary link is down and that has no usable backup --,
+    ``looped`` -- the weight the backups forward in a circle --, ``unrouted``
+    -- the weight without a route on the intact fabric; ``peak`` -- the largest
+    link load -- and ``peak_link``, the first ``(src_dpid, dst_dpid)`` in link
+    order that attains it, None where nothing is carried.  ``base``: the
+    :class:`LinkLoads` of the intact fabric
+    (:meth:`TopologyDB.least_cost_link_loads`).  ``items``: the (scenario,
+    destination switch) items the kernel had to recompute."""
+
+    def __init__(self, scenarios, load, stat, peak, peak_link, base, hkey, hload, result, items):
+        self.scenarios = scenarios
+        self.load = load
+        self.repaired, self.dropped = stat[:, 0].copy(), stat[:, 1].copy()
+        self.looped, self.unrouted = stat[:, 2].copy(), stat[:, 3].copy()
+        self.peak = peak
+        self.peak_link = peak_link
+        self.base = base
+        self.items = items
+        self._hkey, self._hload, self._result = hkey, hload, result
+
+    def __len__(self):
+        return len(self.scenarios)
+
+    def scenario(self, i):
+        """The :class:`LinkLoads` of scenario ``i``: its link loads, and the
+        last hops of the pairs that are delivered."""
+        if self.load is None:
+            raise ValueError("the load planes were not kept (planes=False)")
+        if not 0 <= i < len(self.scenarios):
+            raise IndexError("no scenario %r" % (i,))
+        return self._result(self.load[i], self._hkey, self._hload[i])
 
 
 class CostTuning(object):
@@ -2372,6 +2414,101 @@ class TopologyDB(object):
         :meth:`mpi_link_loads`)."""
         pairs, weights = self._rank_pairs(rank_to_mac, traffic)
         return self.failure_link_loads(failures, pairs, weights, split)
+
+    # -- fast-reroute what-if ----------------------------------------------
+    def _frr_switch_loads(self, ex, edges, sv, dv, w, node_protect, planes):
+        """(load uint64 [nscen, E] or None, stat uint64 [nscen, 4], delivered
+        bool [nscen, n] or None, peak, peak_edge, items) of switch pairs (dense
+        ids sv -> dv, weights w u64) per failure scenario while the loop-free
+        alternates forward: sdnr_frr_link_loads over the least-cost memo's
+        next-hop rows and :meth:`_lfa_rows`, the scenarios in chunks that fit
+        the table budget."""
+        E, n = int(ex.csr.E), int(sv.shape[0])
+        nscen = len(edges)
+        bk = self._lfa_rows(ex, node_protect)[0]
+        nh = self._cost_memo["pall"][1]
+        if n == 0 or not edges:
+            return (np.zeros((nscen, E), np.uint64) if planes else None,
+                    np.zeros((nscen, 4), np.uint64),
+                    np.zeros((nscen, n), bool) if planes else None, np.zeros(nscen, np.uint64),
+                    np.full(nscen, -1, np.int32), 0)
+        dsts, rows = np.unique(dv, return_inverse=True)
+        load, stat, status, peak, pedge, items = self.engine.frr_link_loads(
+            ex, _take(nh, dsts), _take(bk, dsts), dsts, rows.reshape(-1), sv, w, edges,
+            planes=planes, table_budget=self._budget)
+        delivered = None if status is None else (status == 1) | (status == 2)
+        return load, stat, delivered, peak, pedge, items
+
+    def _frr_result(self, ex, scen, got, base, hkey, hload):
+        load, stat, _, peak, pedge, items = got
+        link_of = self._edge_links(ex)
+        link = [None if e < 0 else link_of(e) for e in pedge.tolist()]
+        return FrrLoads(scen, load, stat, peak, link, base, hkey, hload,
+                        lambda ld, hk, hl: self._link_loads_result(ex, ld, hk, hl, LinkLoads),
+                        items)
+
+    def frr_link_loads(self, failures, pairs, weights=None, node_protect=True, planes=True):
+        """What every link carries while FAST REROUTE bridges a failure: the
+        switches forward over their primaries (:meth:`least_cost_tables`'
+        ``nh``) and, where a scenario of ``failures`` took a primary link, over
+        their loop-free alternate (:meth:`lfa_tables`' ``backup``, the second
+        bucket of a fast-failover group) -- before the controller re-routes;
+        :meth:`failure_link_loads` is the state after it has.  A
+        :class:`FrrLoads`; scenarios as in :meth:`failure_link_loads`.
+
+        A switch whose primary link toward a destination is down and that has
+        no alternate, or whose alternate's link is down too, drops that
+        destination's traffic.  With more than one link down the alternates
+        of different switches may forward in a circle (RFC 5286 promises loop
+        freedom for the one failure an alternate was computed for).  Only
+        delivered pairs load links and last hops; the weights of the others
+        are in ``dropped``, ``looped`` and ``unrouted``.
+
+        Defining property: ``scenario(k).as_dict()`` is the weighted count of
+        the ``(dpid, out_port)`` entries of the delivered pairs' walks over
+        those two tables.  Exact uint64 sums.  ``node_protect`` as in
+        :meth:`lfa_tables` (and its ValueErrors).  ``planes=False``: only the
+        per-scenario numbers are kept and ``scenario(k)`` raises -- the form
+        for an N-1 sweep.  Nothing of this object changes: not ``links``, the
+        costs, the memo or the graph on the GPU.  One kernel (frr_loads.hip)
+        recomputes the (scenario, destination) items a failed link touches;
+        scenarios are processed in chunks whose planes fit the table budget."""
+        pairs = list(pairs)
+        weights = None if weights is None else list(weights)
+        ex = self.graph()
+        scen, edges = self._failure_edges(ex, failures)
+        w, dv, last, ok, inv, ssv, sdv, sw = self._switch_pairs(ex, pairs, weights)
+        got = self._frr_switch_loads(ex, edges, ssv, sdv, sw, node_protect, planes)
+        hkey = hload = None
+        if planes:
+            hkey, hload, _ = self._scenario_last_hops(got[2], w, dv, last, ok, inv)
+        base = self.least_cost_link_loads(pairs, weights)
+        return self._frr_result(ex, scen, got, base, hkey, hload)
+
+    def all_pairs_frr_link_loads(self, failures, node_protect=True, planes=True):
+        """:meth:`frr_link_loads` over every ordered pair of distinct hosts
+        with weight 1, from the per-switch host counts (as
+        :meth:`all_pairs_link_loads`)."""
+        if any(self._mac_to_int(m) in self.switches for m in self.hosts):
+            macs = list(self.hosts)
+            return self.frr_link_loads(failures, [(a, b) for a in macs for b in macs if a != b],
+                                       None, node_protect, planes)
+        ex = self.graph()
+        scen, edges = self._failure_edges(ex, failures)
+        sv, dv, w, hv, hc = self._all_pairs_demand(ex)
+        got = self._frr_switch_loads(ex, edges, sv, dv, w, node_protect, planes)
+        hkey = hload = None
+        if planes:
+            hkey, hload, _ = self._all_pairs_scenario_last_hops(ex, got[2], hv, hc, w)
+        base = self.all_pairs_least_cost_link_loads()
+        return self._frr_result(ex, scen, got, base, hkey, hload)
+
+    def mpi_frr_link_loads(self, failures, rank_to_mac, traffic=None, node_protect=True,
+                           planes=True):
+        """:meth:`frr_link_loads` of an MPI job (``traffic`` as in
+        :meth:`mpi_link_loads`)."""
+        pairs, weights = self._rank_pairs(rank_to_mac, traffic)
+        return self.frr_link_loads(failures, pairs, weights, node_protect, planes)
 
     # -- link-cost what-if and the cost tuner -----------------------------
     @staticmethod
