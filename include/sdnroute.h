@@ -867,6 +867,83 @@ int sdnr_fair_rates(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nro
                     double *level, int32_t max_rounds, double *used,
                     int32_t *nrounds /* host */, uint32_t flags);
 
+/* Max-min fair completion times: when every flow of an exchange ends.  The
+ * fluid model behind sdnr_fair_rates has an exact answer: the flows share
+ * max-min fairly, a flow that has sent its bytes leaves, the others are
+ * refilled.  This is the one statement of the definition; fair_times.hip and
+ * engine.fair_times_host follow it step for step.
+ * Flows and initial classification.  Flows, multiplicities, extras,
+ * capacities, rows, layouts and SDNR_LOADS_TO_ROOT are exactly those of
+ * sdnr_fair_rates.  Each flow also has bytes[i], an f64 that is finite and
+ * >= 0: the size of each of the flow's mult[i] identical parallel flows.
+ * rem_b[i] = bytes[i], t = 0.0, carried[e] = 0.0 over the E + nextra entries.
+ *   - Absent flows, with time = +inf, epoch = -1, rate0 = 0.0: a vertex
+ *     outside [0, V) or unreached in its row; multiplicity 0; every flow of a
+ *     rejected row.
+ *   - A routed flow at its row's root with no extra: time = 0.0, epoch = -1,
+ *     rate0 = +inf.
+ *   - A routed flow with bytes == 0: time = 0.0, epoch = -1.  It never takes
+ *     part in the sharing.  Its rate0 is what sdnr_fair_rates gives the same
+ *     call with that flow's multiplicity set to 0 (0.0).
+ *   - Every other flow is in flight.
+ * Epoch j = 0, 1, ...:
+ *   1. Fill.  sdnr_fair_rates' progressive filling, steps 1-4 and the closing
+ *      step 2, unchanged and with the same operation order, over the flows in
+ *      flight: rate[i], the epoch's used[e] and its round count.  rate0 is the
+ *      rate of epoch 0 (with max_epochs == 0 no filling runs and the flows in
+ *      flight keep rate0 = 0.0).
+ *   2. Advance.  q[i] = rem_b[i] / rate[i]; dt = min q over the flows in
+ *      flight; t_j = t_{j-1} + dt; carried[e] += used[e] * dt, the multiply and
+ *      the add each rounded on their own (no FMA).  A flow finishes iff
+ *      q[i] == dt, or rem_b[i] - rate[i] * dt <= 0.0 with the multiply and the
+ *      subtract rounded separately: it gets time = t_j, epoch = j and leaves.
+ *      Otherwise rem_b[i] becomes that difference.
+ *   3. End when nothing is in flight.  Every epoch removes a flow, so there are
+ *      at most as many epochs as flows.
+ * The epoch cap.  When max_epochs epochs have run and flows are still in
+ * flight, those keep time = +inf and epoch = -2, their remaining[i] is what is
+ * left, and *nepochs = max_epochs.
+ * Ties.  There is no tie tolerance, as in sdnr_fair_rates: flows that end at
+ * the same instant as fractions may round one ulp of dt apart and then leave
+ * in two consecutive epochs.  Each such epoch costs a filling and changes no
+ * time beyond rounding.
+ *   time [npairs] f64, epoch [npairs] i32, rate0 [npairs] f64, remaining
+ *         [npairs] f64 (0.0 for a flow that finished, bytes[i] for an absent
+ *         one), at the flows' indices: WRITTEN for pair_off[0] ..
+ *         pair_off[nrows];
+ *   epoch_time [max_epochs] f64, epoch_rounds [max_epochs] i32: t_j and the
+ *         rounds of epoch j's filling, written for j < *nepochs;
+ *   carried [E + nextra] f64: the bytes every link and extra carried;
+ *   nepochs  HOST int32: the epochs run, written before the call returns.
+ * Device pointers only (flags must hold SDNR_DEVICE_PTRS), on the primary
+ * device of a multi-device context.  No grid-wide barrier, and the host knows
+ * neither the round nor the epoch: a clock in device memory (phase, epoch,
+ * round) tells every queued launch what to do, and the last workgroup of an
+ * entry pass advances it.  A step is two launches on the context's stream (a
+ * row kernel -- sdnr_last_kernel names its form, "fair_times_rows_kernel<lds>"
+ * or "fair_times_rows_kernel<global>", chosen as in sdnr_fair_rates -- and a
+ * kernel over the E + nextra entries).  Epoch j with K_j = epoch_rounds[j]
+ * rounds takes K_j + 2 steps and the step that finds nothing in flight (or the
+ * cap reached) one more: S = sum over j < *nepochs of (K_j + 2), plus 1.  Steps
+ * are queued 16 at a time and the call waits for the clock's 16 bytes per
+ * batch, so it returns when the epochs are done (every output is final then)
+ * and sdnr_last_launches is 1 + 32 * ceil(S / 16).  SDNR_TIMING as in
+ * sdnr_fair_rates.  nrows == 0 or no pairs: SDNR_OK, *nepochs = 0, nothing
+ * else touched.  pair_off[0] > pair_off[nrows] is SDNR_ERR_INVAL at once.  A
+ * row that is not a tree of the graph, offsets of a row outside the pair list,
+ * a capacity that is not positive and finite (taken as +inf), an extra outside
+ * [E, E + nextra) (ignored) and a byte size that is negative or not finite
+ * (that flow is absent) are reported by sdnr_synchronize as SDNR_ERR_INVAL;
+ * the other rows' flows are what they are without such a row. */
+int sdnr_fair_times(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nrows,
+                    const int64_t *pair_off, const int32_t *verts, const uint64_t *mult,
+                    const double *bytes, const int32_t *extra /* [npairs][2] or NULL */,
+                    const double *cap, int32_t nextra, double *time, int32_t *epoch,
+                    double *rate0, double *remaining, double *epoch_time /* [max_epochs] */,
+                    int32_t *epoch_rounds /* [max_epochs] */, int32_t max_epochs,
+                    double *carried /* [E + nextra] */, int32_t *nepochs /* host */,
+                    uint32_t flags);
+
 /* Max-min fair rates of flows split over EVERY least-cost route (ECMP): what
  * sdnr_fair_rates answers for one path per pair, for the fabric as it is run.
  * This is the one statement of the definition; ecmp_fair_rates.hip and
@@ -968,7 +1045,7 @@ int sdnr_last_launches(const sdnr_ctx *ctx, int32_t *launches);
  * kernels of sdnr_link_loads, sdnr_ecmp_link_loads, sdnr_cost_ecmp_link_loads,
  * sdnr_cost_tables, sdnr_widest_tables, sdnr_failure_ecmp_link_loads,
  * sdnr_whatif_ecmp_link_loads, sdnr_lfa_tables, sdnr_fair_rates,
- * sdnr_ecmp_fair_rates (their row kernel), sdnr_multicast_trees,
+ * sdnr_ecmp_fair_rates, sdnr_fair_times (their row kernel), sdnr_multicast_trees,
  * sdnr_frr_link_loads (its item kernel, over the affected items) and
  * sdnr_ecmp_counts give every workgroup the rows (batches, items, groups) r,
  * r + grid, r + 2 * grid, ...: with more units of work than this a workgroup

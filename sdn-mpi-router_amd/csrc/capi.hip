@@ -108,6 +108,12 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "a tree link the graph lacks: that row's flows read 0), pair_off "
                              "outside the pair list, a capacity that is not a positive finite "
                              "number or an extra outside [E, E + nextra): rates invalid");
+        if (h & kErrFairTimes)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_fair_times: a row is not a tree of the uploaded "
+                             "graph (that row's flows are absent), pair_off outside the pair list, "
+                             "a capacity that is not a positive finite number, an extra outside "
+                             "[E, E + nextra) or a byte size that is negative or not finite (that "
+                             "flow is absent): times invalid");
         if (h & kErrEcmpFairRates)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_rates: a pcost row is not a "
                              "least-cost labelling of the uploaded graph under the costs in force "
@@ -1534,6 +1540,41 @@ int sdnr_fair_rates(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nro
     return sdnr_launch_fair_rates(ctx, tree, layout, to_root, nrows, pair_off, lo, hi, verts, mult,
                                   extra, cap, nextra, rate, bott, round, level, max_rounds, used,
                                   nrounds);
+}
+
+int sdnr_fair_times(sdnr_ctx *ctx, const void *tree, int32_t layout, int32_t nrows,
+                    const int64_t *pair_off, const int32_t *verts, const uint64_t *mult,
+                    const double *bytes, const int32_t *extra, const double *cap, int32_t nextra,
+                    double *time, int32_t *epoch, double *rate0, double *remaining,
+                    double *epoch_time, int32_t *epoch_rounds, int32_t max_epochs, double *carried,
+                    int32_t *nepochs, uint32_t flags)
+{
+    static const char name[] = "sdnr_fair_times";
+    CHECK_CTX(ctx);
+    if (!nepochs) return sdnr_fail(SDNR_ERR_INVAL, "%s: null nepochs", name);
+    *nepochs = 0;
+    int rc = open_pair_call(ctx, flags, nrows < 0 || nextra < 0 || max_epochs < 0, name);
+    if (rc) return rc;
+    if ((int64_t)ctx->E + nextra > 0x7FFFFFFF)
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: E + nextra = %lld is no int32", name,
+                         (long long)ctx->E + nextra);
+    const bool to_root = (flags & SDNR_LOADS_TO_ROOT) != 0;
+    if ((rc = check_tree_layout(ctx, layout, to_root, name, "SDNR_LOADS_TO_ROOT"))) return rc;
+    if (nrows == 0) return SDNR_OK;
+    if (!tree || !pair_off) return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
+    SDNR_HIP(hipSetDevice(ctx->device));
+    int64_t lo, hi;
+    bool empty;
+    if ((rc = list_bounds(ctx, pair_off, nrows, name, "pair_off", &lo, &hi, &empty))) return rc;
+    if (empty) return SDNR_OK;
+    if (!verts || !bytes || !time || !epoch || !rate0 || !remaining ||
+        ((!epoch_time || !epoch_rounds) && max_epochs > 0) ||
+        ((!cap || !carried) && ctx->E + nextra > 0))
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
+    ctx->timed = (flags & SDNR_TIMING) != 0;
+    return sdnr_launch_fair_times(ctx, tree, layout, to_root, nrows, pair_off, lo, hi, verts, mult,
+                                  bytes, extra, cap, nextra, time, epoch, rate0, remaining,
+                                  epoch_time, epoch_rounds, max_epochs, carried, nepochs);
 }
 
 int sdnr_ecmp_fair_rates(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrows,

@@ -52,7 +52,8 @@ __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "WIDEST_LDS_MAX_V", "WIDEST_LDS_B4_MAX_V", "WIDEST_LDS_B6_MAX_V", "fair_rates_host",
            "check_fair_flows", "FAIR_LDS_MAX_V", "FAIR_MULT_LIMIT", "ecmp_fair_rates_host",
            "ECMP_FAIR_LDS_MAX_V", "FAIR_TIE", "multicast_trees_host", "MCAST_LDS_BYTES",
-           "multicast_maps_in_lds"]
+           "multicast_maps_in_lds", "fair_times_host", "check_fair_bytes", "fair_times_launches",
+           "FAIR_TIMES_BATCH"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -644,6 +645,120 @@ def fair_rates_host(csr, tree, layout, rows, verts, mult, cap, extra=None, to_ro
     else:
         raise AssertionError("fair_rates_host: a round froze no flow")
     return rate, bott, rnd, np.asarray(level, np.float64), used
+
+
+FAIR_TIMES_BATCH = 16           # csrc/fair_rows.h kFairBatch: steps queued per status read-back
+
+
+def check_fair_bytes(n, nbytes):
+    """float64 [n] byte sizes of sdnr_fair_times' flows (one number: the same
+    for all), finite and >= 0."""
+    nbytes = np.asarray(nbytes, np.float64)
+    if nbytes.ndim == 0:
+        nbytes = np.full(n, float(nbytes), np.float64)
+    nbytes = np.ascontiguousarray(nbytes.reshape(-1))
+    if nbytes.shape[0] != n:
+        raise ValueError("fair times: %d byte sizes for %d flows" % (nbytes.shape[0], n))
+    if not bool((np.isfinite(nbytes) & (nbytes >= 0)).all()):
+        raise ValueError("fair times: byte sizes must be finite and not negative")
+    return nbytes
+
+
+def _fair_epoch_cap(n, max_epochs):
+    """sdnr_fair_times' max_epochs: every epoch removes a flow, so n epochs
+    always suffice."""
+    if max_epochs is None:
+        return n
+    if int(max_epochs) < 0:
+        raise ValueError("fair times: max_epochs must not be negative")
+    return min(int(max_epochs), n)
+
+
+def fair_times_launches(epoch_rounds):
+    """sdnr_last_launches after a sdnr_fair_times call that ran epochs of
+    ``epoch_rounds`` rounds: epoch j takes epoch_rounds[j] + 2 steps, the step
+    that finds nothing in flight (or the cap reached) one more; a step is two
+    launches, steps are queued FAIR_TIMES_BATCH at a time, and one launch
+    starts the call."""
+    steps = int(np.sum(np.asarray(epoch_rounds, np.int64) + 2)) + 1
+    return 1 + 2 * FAIR_TIMES_BATCH * (-(-steps // FAIR_TIMES_BATCH))
+
+
+def fair_times_host(csr, tree, layout, rows, verts, mult, nbytes, cap, extra=None, to_root=False,
+                    max_epochs=None):
+    """numpy restatement of sdnr_fair_times (the CPU tests' engine double and
+    the checker of fair_times.hip): max-min fair completion times.  The flows
+    of ``fair_rates_host`` each send ``nbytes[i]`` bytes (per parallel flow of
+    their multiplicity); they share max-min fairly, a flow that has sent its
+    bytes leaves, the others are refilled.  Returns ``(time float64 [n], epoch
+    int32 [n], rate0 float64 [n], remaining float64 [n], epoch_time float64
+    [epochs], epoch_rounds int32 [epochs], carried float64 [E + nextra])``.
+
+    The definition is sdnroute.h's, step for step: every epoch is one
+    ``fair_rates_host`` call with the departed flows' multiplicity set to 0,
+    then ``q = rem_b / rate``, ``dt = min q``, ``carried += used * dt``, and a
+    flow finishes iff ``q == dt`` or ``rem_b - rate * dt <= 0`` -- every
+    operation a numpy operation of its own, so the device results are these bit
+    for bit.  Absent flows read +inf / -1 / 0.0, a flow at the row's root
+    without an extra 0.0 / -1 / +inf, a routed flow without bytes 0.0 / -1 /
+    0.0; with ``max_epochs`` reached the flows still in flight read +inf / -2
+    and what they have left."""
+    E = int(csr.E)
+    rows = np.asarray(rows, np.int64).reshape(-1)
+    n = rows.shape[0]
+    mult, cap, extra_all, nextra = check_fair_flows(E, n, mult, cap, extra)
+    nbytes = check_fair_bytes(n, nbytes)
+    most = _fair_epoch_cap(n, max_epochs)
+    inf = np.float64(np.inf)
+    time = np.full(n, inf)
+    epoch = np.full(n, -1, np.int32)
+    left = nbytes.copy()
+    carried = np.zeros(E + nextra, np.float64)
+    e_time, e_rounds = [], []
+    fill = lambda m: fair_rates_host(csr, tree, layout, rows, verts, m, cap, extra, to_root)  # noqa
+    if n == 0:
+        return (time, epoch, np.zeros(0, np.float64), left, np.zeros(0, np.float64),
+                np.zeros(0, np.int32), carried)
+    empty = (nbytes == 0) & (mult > 0)
+    m = np.where(empty, np.uint64(0), mult)
+    rate0, _, rnd, level, used = fill(m)
+    if empty.any():
+        # a flow without bytes is classified as it is routed, then takes no share
+        r_all, _, k_all, _, _ = fill(mult)
+        rate0[empty & np.isinf(r_all)] = inf
+        time[empty & (np.isinf(r_all) | (k_all >= 0))] = 0.0
+    bare = np.isinf(rate0)
+    time[bare] = 0.0
+    left[bare] = 0.0
+    rate, t = rate0, np.float64(0.0)
+    for j in range(n + 1):
+        fl = np.nonzero(rnd >= 0)[0]                       # in flight
+        if fl.size == 0:
+            break
+        if j == most:
+            epoch[fl] = -2
+            if j == 0:
+                rate0[fl] = 0.0                            # (no filling ran)
+            break
+        q = left[fl] / rate[fl]
+        dt = q.min()
+        if not np.isfinite(dt):
+            break
+        t = t + dt
+        carried = carried + used * dt
+        rest = left[fl] - rate[fl] * dt
+        done = (q == dt) | (rest <= 0.0)
+        time[fl[done]] = t
+        epoch[fl[done]] = j
+        left[fl] = np.where(done, 0.0, rest)
+        m[fl[done]] = 0
+        e_time.append(t)
+        e_rounds.append(len(level))
+        rate, _, rnd, level, used = fill(m)
+    else:
+        raise AssertionError("fair_times_host: an epoch removed no flow")
+    return (time, epoch, rate0, left, np.asarray(e_time, np.float64),
+            np.asarray(e_rounds, np.int32), carried)
 
 
 SPLITS = ("route", "hop")
@@ -1985,30 +2100,12 @@ class RouteEngine(object):
         the element size it must have) and ``launch(table pointer, nrows,
         ...)`` the entry point, which returns the number of rounds."""
         t = self._torch
-        V, E = int(export.csr.V), int(export.csr.E)
-        rows = np.asarray(rows, np.int64).reshape(-1)
-        n = rows.shape[0]
-        if cap is None:
-            cap = np.ones(E, np.float64)
-        mult_in = mult
-        mult, cap, extra_all, nextra = check_fair_flows(E, n, mult, cap, extra)
-        NE = E + nextra
-        nrows = int(table.shape[0])
-        if n == 0 or nrows == 0:
-            if n:
-                raise ValueError("%s: a pair names a row outside the table" % what)
+        f = self._fair_flows_device(what, export, table, rows, verts, mult, cap, extra, word)
+        n, NE, nextra, nrows, order = f.n, f.NE, f.nextra, f.nrows, f.order
+        if order is None:
             return (np.zeros(0, np.float64), np.zeros(0, np.int32), np.zeros(0, np.int32),
                     np.zeros(0, np.float64), np.zeros(NE, np.float64))
-        order, off, x, m = _pairs_for_device(rows, nrows, verts, V,
-                                             None if mult_in is None else mult, what)
-        if word is not None and table.element_size() != word:
-            raise ValueError("%s: pcost rows are 32-bit" % what)
-        table = table.contiguous()
-        d_off, d_x, d_m = self._upload_pairs(off, x, m)
-        d_e = None
-        if extra is not None:
-            d_e = t.from_numpy(np.ascontiguousarray(extra_all[order].astype(np.int32))).to(self.dev)
-        d_cap = t.from_numpy(cap).to(self.dev)
+        table, d_off, d_x, d_m, d_e, d_cap = f.table, f.d_off, f.d_x, f.d_m, f.d_e, f.d_cap
         max_rounds = min(n, NE)
         rate = t.empty(n, dtype=t.float64, device=self.dev)
         bott = t.empty(n, dtype=t.int32, device=self.dev)
@@ -2024,6 +2121,84 @@ class RouteEngine(object):
         self.ctx.synchronize()              # raises if a row was no tree / least-cost labelling
         rate, bott, rnd = (_unsorted(a.cpu().numpy(), order) for a in (rate, bott, rnd))
         return rate, bott, rnd, level.cpu().numpy()[:rounds], used.cpu().numpy()
+
+    _FairFlows = collections.namedtuple(
+        "_FairFlows", "n NE nextra nrows order table d_off d_x d_m d_e d_cap")
+
+    def _fair_flows_device(self, what, export, table, rows, verts, mult, cap, extra, word=None):
+        """The flows of a fair-sharing call, checked (``check_fair_flows``),
+        sorted by row and uploaded: what ``_fair_rates_over`` and
+        ``fair_times`` launch over.  ``order`` is None when there is no flow
+        (nothing was uploaded then)."""
+        t = self._torch
+        V, E = int(export.csr.V), int(export.csr.E)
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        n = rows.shape[0]
+        if cap is None:
+            cap = np.ones(E, np.float64)
+        mult_in = mult
+        mult, cap, extra_all, nextra = check_fair_flows(E, n, mult, cap, extra)
+        NE = E + nextra
+        nrows = int(table.shape[0])
+        if n == 0 or nrows == 0:
+            if n:
+                raise ValueError("%s: a pair names a row outside the table" % what)
+            return self._FairFlows(n, NE, nextra, nrows, None, table, *([None] * 5))
+        order, off, x, m = _pairs_for_device(rows, nrows, verts, V,
+                                             None if mult_in is None else mult, what)
+        if word is not None and table.element_size() != word:
+            raise ValueError("%s: pcost rows are 32-bit" % what)
+        table = table.contiguous()
+        d_off, d_x, d_m = self._upload_pairs(off, x, m)
+        d_e = None
+        if extra is not None:
+            d_e = t.from_numpy(np.ascontiguousarray(extra_all[order].astype(np.int32))).to(self.dev)
+        d_cap = t.from_numpy(cap).to(self.dev)
+        return self._FairFlows(n, NE, nextra, nrows, order, table, d_off, d_x, d_m, d_e, d_cap)
+
+    def fair_times(self, export, tree, layout, rows, verts, mult=None, nbytes=1.0, cap=None,
+                   extra=None, to_root=False, max_epochs=None, timing=False):
+        """Max-min fair completion times of flows routed over device tree rows
+        (fair_times.hip, sdnr_fair_times): ``(time float64 [n], epoch int32
+        [n], rate0 float64 [n], remaining float64 [n], epoch_time float64
+        [epochs], epoch_rounds int32 [epochs], carried float64 [E + nextra])``
+        in the flows' order, bit for bit what ``fair_times_host`` returns.
+
+        The flows, ``mult``, ``cap``, ``extra`` and ``to_root`` as in
+        ``fair_rates``; ``nbytes``: float64 [n] (or one number for all), the
+        size of each of flow i's ``mult[i]`` parallel flows, finite and >= 0;
+        ``max_epochs``: stop after that many departures' epochs (None: run to
+        the end).  The epochs and their fillings advance on the device; the
+        host reads one status word per batch of launches."""
+        self.load(export)
+        t = self._torch
+        f = self._fair_flows_device("fair_times", export, tree, rows, verts, mult, cap, extra)
+        n, NE = f.n, f.NE
+        nbytes = check_fair_bytes(n, nbytes)
+        cap_e = _fair_epoch_cap(n, max_epochs)
+        if f.order is None:
+            return (np.zeros(0, np.float64), np.zeros(0, np.int32), np.zeros(0, np.float64),
+                    np.zeros(0, np.float64), np.zeros(0, np.float64), np.zeros(0, np.int32),
+                    np.zeros(NE, np.float64))
+        d_b = t.from_numpy(np.ascontiguousarray(nbytes[f.order])).to(self.dev)
+        time, rate0, left = (t.empty(n, dtype=t.float64, device=self.dev) for _ in range(3))
+        epoch = t.empty(n, dtype=t.int32, device=self.dev)
+        e_time = t.empty(cap_e, dtype=t.float64, device=self.dev)
+        e_rounds = t.empty(cap_e, dtype=t.int32, device=self.dev)
+        carried = t.zeros(NE, dtype=t.float64, device=self.dev)
+        self._ready()
+        epochs = self.ctx.fair_times_device(
+            f.table.data_ptr(), self._layout_code(layout), f.nrows, f.d_off.data_ptr(),
+            f.d_x.data_ptr(), _ptr(f.d_m), d_b.data_ptr(), _ptr(f.d_e),
+            f.d_cap.data_ptr() if NE else 0, f.nextra, time.data_ptr(), epoch.data_ptr(),
+            rate0.data_ptr(), left.data_ptr(), e_time.data_ptr() if cap_e else 0,
+            e_rounds.data_ptr() if cap_e else 0, cap_e, carried.data_ptr() if NE else 0,
+            to_root=to_root, timing=timing)
+        self.ctx.synchronize()              # raises if a row was no tree
+        time, epoch, rate0, left = (_unsorted(a.cpu().numpy(), f.order)
+                                    for a in (time, epoch, rate0, left))
+        return (time, epoch, rate0, left, e_time.cpu().numpy()[:epochs],
+                e_rounds.cpu().numpy()[:epochs], carried.cpu().numpy())
 
     def ecmp_link_loads(self, export, dist, rows, srcs, weights=None, split="route",
                         timing=False):

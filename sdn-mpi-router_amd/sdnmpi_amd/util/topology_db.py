@@ -384,6 +384,50 @@ class FairRates(object):
         return float(self.time.max()) if self.time.size else 0.0
 
 
+class FlowTimes(object):
+    """Predicted max-min fair completion times
+    (:meth:`TopologyDB.fair_completion_times`).
+
+    Per input pair, in the order given: ``pairs``, ``weights`` (uint64
+    multiplicities), ``bytes`` (float64, per flow), ``time`` (float64: when
+    each flow of the pair has sent its bytes; 0.0 for a routed pair without
+    bytes or one that crosses nothing modelled, ``inf`` for an unrouted pair,
+    one of weight 0 and one still sending when ``max_epochs`` ran out),
+    ``epoch`` (int32: the epoch the pair left in; -1 where it never shared, -2
+    still sending), ``routed`` (bool), ``rate0`` (float64: the pair's rate at
+    t = 0, :meth:`TopologyDB.fair_rates`' ``rate``) and ``remaining`` (float64:
+    bytes not sent yet).  ``epoch_time[j]`` is when epoch j ended and
+    ``epoch_rounds[j]`` the rounds of its filling, ``epochs`` their number;
+    ``link_bytes`` is a :class:`SplitLinkLoads` of the bytes every link
+    carried (last hops: the bytes out of every host port, when host ports are
+    modelled); ``complete`` says that no pair is still sending."""
+
+    def __init__(self, pairs, weights, nbytes, time, epoch, routed, rate0, remaining, epoch_time,
+                 epoch_rounds, link_bytes):
+        self.pairs = pairs
+        self.weights = weights
+        self.bytes = nbytes
+        self.time = time
+        self.epoch = epoch
+        self.routed = routed
+        self.rate0 = rate0
+        self.remaining = remaining
+        self.epoch_time = epoch_time
+        self.epoch_rounds = epoch_rounds
+        self.epochs = int(epoch_time.shape[0])
+        self.link_bytes = link_bytes
+        self.complete = not bool((epoch == -2).any())
+
+    def makespan(self):
+        """How long the exchange takes: the largest finite ``time`` (0.0
+        without one), or ``inf`` if a pair of nonzero weight with bytes to
+        send has no route."""
+        if bool((~self.routed & (self.bytes > 0) & (self.weights != 0)).any()):
+            return float("inf")
+        t = self.time[np.isfinite(self.time)]
+        return float(t.max()) if t.size else 0.0
+
+
 def _weights(weights, n):
     """u64 weights of n pairs (None: ones); negative or oversized: ValueError."""
     if weights is None:
@@ -2872,26 +2916,13 @@ class TopologyDB(object):
             return np.full(E, float(capacity), np.float64)
         return self._capacity_vector(ex, capacity)
 
-    def _fair(self, ex, pairs, w, sv, dv, ports, capacity, host_capacity, route, split="route"):
-        """FairRates of pairs already resolved: dense switches sv -> dv (-1:
-        unknown host), multiplicities w, and per pair ``ports`` = (source
-        switch port, destination switch port, source MAC, destination MAC) for
-        the host-port constraints (None: not modelled)."""
-        if split not in ("route", "hop"):
-            raise ValueError("split must be 'route' or 'hop'")
-        if route not in self.FAIR_ROUTES + self.FAIR_ECMP_ROUTES:
-            raise ValueError("route must be one of %s" % ", ".join(
-                map(repr, self.FAIR_ROUTES + self.FAIR_ECMP_ROUTES)))
-        if route in self.FAIR_ECMP_ROUTES and not hasattr(self.engine, "ecmp_fair_rates"):
-            # (a missing kernel is an error, never a fall-back to one path per pair)
-            raise ValueError("route=%r needs an engine with ecmp_fair_rates (the multipath "
-                             "filling); this one offers only the single-path routes %s"
-                             % (route, ", ".join(map(repr, self.FAIR_ROUTES))))
-        if split != "route" and route not in self.FAIR_ECMP_ROUTES:
-            raise ValueError("split=%r needs a multipath route (%s): %r puts a pair on one path"
-                             % (split, ", ".join(map(repr, self.FAIR_ECMP_ROUTES)), route))
-        n = sv.shape[0]
-        E, V = int(ex.csr.E), int(ex.csr.V)
+    def _fair_classes(self, ex, w, sv, dv, ports, capacity, host_capacity):
+        """What the pairs of a fair-sharing call are told apart by: (cap
+        float64 [E + extras], ok -- the pairs with known hosts --, hkey -- the
+        last hops' (switch, port) --, nin -- the number of ports into the
+        fabric, the first extras --, macs -- a MAC per extra --, cols -- per ok
+        pair its switches and, with host ports, its two extras)."""
+        E = int(ex.csr.E)
         if sum(int(x) for x in w.tolist()) >= FAIR_MULT_LIMIT:
             raise ValueError("fair rates: the weights must sum below 2**53")
         cap = self._fair_capacity(ex, capacity)
@@ -2923,6 +2954,30 @@ class TopologyDB(object):
                 macs[nin + hinv[j]] = macs[nin + hinv[j]] or ports[3][i]
             cols = np.stack([sv[ok], dv[ok], E + iinv, E + nin + hinv], 1).reshape(-1, 4)
             cap = np.concatenate([cap, np.full(len(macs), float(host_capacity), np.float64)])
+        return cap, ok, hkey, nin, macs, cols
+
+    def _fair(self, ex, pairs, w, sv, dv, ports, capacity, host_capacity, route, split="route"):
+        """FairRates of pairs already resolved: dense switches sv -> dv (-1:
+        unknown host), multiplicities w, and per pair ``ports`` = (source
+        switch port, destination switch port, source MAC, destination MAC) for
+        the host-port constraints (None: not modelled)."""
+        if split not in ("route", "hop"):
+            raise ValueError("split must be 'route' or 'hop'")
+        if route not in self.FAIR_ROUTES + self.FAIR_ECMP_ROUTES:
+            raise ValueError("route must be one of %s" % ", ".join(
+                map(repr, self.FAIR_ROUTES + self.FAIR_ECMP_ROUTES)))
+        if route in self.FAIR_ECMP_ROUTES and not hasattr(self.engine, "ecmp_fair_rates"):
+            # (a missing kernel is an error, never a fall-back to one path per pair)
+            raise ValueError("route=%r needs an engine with ecmp_fair_rates (the multipath "
+                             "filling); this one offers only the single-path routes %s"
+                             % (route, ", ".join(map(repr, self.FAIR_ROUTES))))
+        if split != "route" and route not in self.FAIR_ECMP_ROUTES:
+            raise ValueError("split=%r needs a multipath route (%s): %r puts a pair on one path"
+                             % (split, ", ".join(map(repr, self.FAIR_ECMP_ROUTES)), route))
+        n = sv.shape[0]
+        E, V = int(ex.csr.E), int(ex.csr.V)
+        cap, ok, hkey, nin, macs, cols = self._fair_classes(ex, w, sv, dv, ports, capacity,
+                                                            host_capacity)
         # pairs -> flows: equal (switches, extras) merge, multiplicities summed
         fkey, finv = np.unique(cols, axis=0, return_inverse=True)
         finv = finv.reshape(-1)
@@ -3049,8 +3104,9 @@ class TopologyDB(object):
         pair without a route, 0.0 for no bytes), and ``step_time()``, the
         largest: the exchange's duration if the rates held throughout -- flows
         that finish early would leave their share to the rest, so the real
-        exchange is no slower than that.  ``route`` and ``split`` as in
-        :meth:`fair_rates`."""
+        exchange is no slower than that (:meth:`mpi_exchange_times` follows
+        the departures and gives the duration itself).  ``route`` and ``split``
+        as in :meth:`fair_rates`."""
         pairs, nbytes = self._rank_pairs(rank_to_mac, traffic)
         res = self.fair_rates(pairs, None, capacity, host_capacity, route, split)
         b = np.ones(len(pairs), np.float64) if nbytes is None else \
@@ -3061,6 +3117,136 @@ class TopologyDB(object):
             t = np.where(b == 0, 0.0, b / res.rate)
         res.bytes, res.time = b, t
         return res
+
+    # -- max-min fair completion times ---------------------------------------
+    def _fair_times(self, ex, pairs, w, nbytes, sv, dv, ports, capacity, host_capacity, route,
+                    max_epochs):
+        """FlowTimes of pairs already resolved, as :meth:`_fair` takes them,
+        each sending ``nbytes[i]`` bytes per flow."""
+        if route not in self.FAIR_ROUTES:
+            # (a missing kernel is an error, never a fall-back to one path per pair)
+            raise ValueError("completion times follow one path per pair: route must be one of %s "
+                             "(got %r)" % (", ".join(map(repr, self.FAIR_ROUTES)), route))
+        n = sv.shape[0]
+        E = int(ex.csr.E)
+        b = np.asarray(nbytes, np.float64)
+        b = np.full(n, float(b), np.float64) if b.ndim == 0 else b.reshape(-1)
+        if b.shape[0] != n:
+            raise ValueError("one byte size per pair")
+        if not bool((np.isfinite(b) & (b >= 0)).all()):
+            raise ValueError("byte sizes must be finite and not negative")
+        b = b + 0.0                                             # (-0.0 is 0.0)
+        if max_epochs is not None and int(max_epochs) < 0:
+            raise ValueError("max_epochs must not be negative")
+        cap, ok, hkey, nin, macs, cols = self._fair_classes(ex, w, sv, dv, ports, capacity,
+                                                            host_capacity)
+        # pairs -> flows: equal (switches, extras, bytes) merge, multiplicities summed
+        cols = np.concatenate([cols, b[ok].view(np.int64).reshape(-1, 1)], 1)
+        fkey, finv = np.unique(cols, axis=0, return_inverse=True)
+        finv = finv.reshape(-1)
+        fw = np.zeros(fkey.shape[0], np.uint64)
+        np.add.at(fw, finv, w[ok])
+        time = np.full(n, np.inf)
+        epoch = np.full(n, -1, np.int32)
+        rate0 = np.zeros(n, np.float64)
+        left = b.copy()
+        routed = np.zeros(n, bool)
+        e_time, e_rounds = np.zeros(0, np.float64), np.zeros(0, np.int32)
+        carried = np.zeros(cap.shape[0], np.float64)
+        if fkey.shape[0]:
+            fs, fd = fkey[:, 0], fkey[:, 1]
+            extra = fkey[:, 2:4] if host_capacity is not None else None
+            fb = np.ascontiguousarray(fkey[:, -1]).view(np.float64)
+            tree, layout, rows, verts, to_root, reach = self._fair_rows(ex, route, fs, fd)
+            # (next-hop rows cannot tell an unreached vertex from the root)
+            verts = np.where(reach, verts, -1)
+            t, k, r0, rest, e_time, e_rounds, carried = self.engine.fair_times(
+                ex, tree, layout, rows, verts, fw, fb, cap, extra, to_root=to_root,
+                max_epochs=max_epochs)
+            time[ok], epoch[ok], rate0[ok], left[ok] = t[finv], k[finv], r0[finv], rest[finv]
+            routed[ok] = reach[finv]
+        link_bytes = self._link_loads_result(ex, carried[:E], hkey, carried[E + nin:],
+                                             SplitLinkLoads)
+        return FlowTimes(pairs, w, b, time, epoch, routed, rate0, left, e_time, e_rounds,
+                         link_bytes)
+
+    def fair_completion_times(self, pairs, nbytes, weights=None, capacity=None,
+                              host_capacity=None, route="default", max_epochs=None):
+        """When every (src_mac, dst_mac) pair of ``pairs`` has sent its
+        ``nbytes[i]`` bytes (one number: the same for all) if all start at
+        once and share the links max-min fairly throughout: a pair that is
+        done leaves and the others are refilled, which :meth:`fair_rates`'
+        ``bytes / rate`` ignores.  Returns a :class:`FlowTimes`.
+
+        ``weights``, ``capacity`` and ``host_capacity`` as in
+        :meth:`fair_rates`; pair i stands for ``weights[i]`` parallel flows of
+        ``nbytes[i]`` bytes each.  ``route``: one of the single-path tables
+        ``"default"``, ``"shortest"``, ``"least_cost"``, ``"least_loaded"``
+        (the multipath routes are a ValueError).  ``max_epochs``: stop after
+        that many departure epochs; the pairs still sending read ``time`` inf,
+        ``epoch`` -2 and what they have left in ``remaining``.  Byte sizes that
+        are negative, NaN or inf are a ValueError.  Pairs merge into one flow
+        class only when switches, host ports and bytes are equal.  The GPU
+        runs the epochs and their fillings (fair_times.hip) from state on the
+        device, bit for bit equal to ``engine.fair_times_host``; there is no
+        tie tolerance, so pairs that end together as fractions may leave one
+        ulp apart in consecutive epochs."""
+        ex = self.graph()
+        pairs = list(pairs)
+        n = len(pairs)
+        w = _weights(weights, n)
+        sv = np.full(n, -1, np.int64)
+        dv = np.full(n, -1, np.int64)
+        sport = np.zeros(n, np.int64)
+        dport = np.zeros(n, np.int64)
+        for i, (a, b) in enumerate(pairs):
+            ea, eb = self._endpoint(a), self._endpoint(b)
+            if ea is None or eb is None:
+                continue
+            sv[i] = ex.index[ea[0]]
+            dv[i] = ex.index[eb[0]]
+            sport[i] = self._last_hop(ea[0], ea[1], a)[1]
+            dport[i] = self._last_hop(eb[0], eb[1], b)[1]
+        ports = (sport, dport, [a for a, _ in pairs], [b for _, b in pairs])
+        return self._fair_times(ex, pairs, w, nbytes, sv, dv, ports, capacity, host_capacity,
+                                route, max_epochs)
+
+    def all_pairs_fair_completion_times(self, nbytes=1.0, capacity=None, route="default",
+                                        max_epochs=None):
+        """:meth:`fair_completion_times` of every ordered pair of distinct
+        hosts at once, ``nbytes`` bytes each (MPI_Alltoall with equal blocks),
+        in the switch-pair form of :meth:`all_pairs_fair_rates` (the MAC-pair
+        form when a host MAC names a switch)."""
+        if isinstance(nbytes, bool) or not isinstance(nbytes, (int, float, np.integer,
+                                                               np.floating)):
+            raise ValueError("nbytes is one number for every pair")
+        if any(self._mac_to_int(m) in self.switches for m in self.hosts):
+            macs = list(self.hosts)
+            return self.fair_completion_times([(a, b) for a in macs for b in macs if a != b],
+                                              nbytes, None, capacity, None, route, max_epochs)
+        ex = self.graph()
+        hv = np.asarray(self._host_vertices(ex), np.int64)
+        hc = np.asarray(ex.host_count, np.int64)
+        n = hv.shape[0]
+        sv, dv = np.repeat(hv, n), np.tile(hv, n)
+        w = (hc[sv] * (hc[dv] - (sv == dv))).astype(np.uint64)
+        dp = ex.csr.dpids
+        pairs = list(zip(dp[sv].tolist(), dp[dv].tolist()))
+        return self._fair_times(ex, pairs, w, nbytes, sv, dv, None, capacity, None, route,
+                                max_epochs)
+
+    def mpi_exchange_times(self, rank_to_mac, traffic=None, capacity=None, host_capacity=None,
+                           route="default", max_epochs=None):
+        """:meth:`fair_completion_times` of an MPI job's exchange: the keys of
+        ``traffic`` = {(src_rank, dst_rank): bytes} give the pairs, one flow
+        each (None: every ordered rank pair i != j, one byte each).
+        ``makespan()`` of the result is how long the exchange takes; it is
+        never above ``mpi_fair_rates(...).step_time()`` beyond rounding."""
+        pairs, nbytes = self._rank_pairs(rank_to_mac, traffic)
+        b = np.ones(len(pairs), np.float64) if nbytes is None else \
+            np.asarray([float(x) for x in nbytes], np.float64).reshape(-1)
+        return self.fair_completion_times(pairs, b, None, capacity, host_capacity, route,
+                                          max_epochs)
 
     def find_routes(self, pairs, multiple=False):
         """find_route over many (src_mac, dst_mac) pairs; tables are computed
