@@ -1023,6 +1023,89 @@ int sdnr_ecmp_fair_rates(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrows,
                          double *level, int32_t max_rounds, double *used,
                          int32_t *nrounds /* host */, uint32_t flags);
 
+/* Max-min fair completion times over ECMP: when every flow of an exchange ends
+ * if each is split over EVERY least-cost route -- what sdnr_fair_times answers
+ * for one path per pair, for the fabric as it is run.  This is the one
+ * statement of the definition; ecmp_fair_times.hip and
+ * engine.ecmp_fair_times_host follow it step for step.
+ * Flows and initial classification.  Flows, fractions, multiplicities, extras,
+ * capacities, costs (none uploaded: every link costs 1) and
+ * SDNR_LOADS_SPLIT_HOP are exactly those of sdnr_ecmp_fair_rates.  Each flow
+ * also has bytes[i], as in sdnr_fair_times: an f64 that is finite and >= 0, the
+ * size of each of the flow's mult[i] identical parallel flows.  rem_b[i] =
+ * bytes[i], t = 0.0, carried[e] = 0.0 over the E + nextra entries.
+ *   - Absent flows, with time = +inf, epoch = -1, rate0 = 0.0: a source outside
+ *     [0, V) or without a route; multiplicity 0; a byte size that is negative or
+ *     not finite; every flow of a row that is no least-cost labelling.
+ *   - A routed flow at the destination (pcost 0) with no extra: time = 0.0,
+ *     epoch = -1, rate0 = +inf, remaining = 0.0.
+ *   - A routed flow with bytes == 0: time = 0.0, epoch = -1.  It never takes
+ *     part in the sharing.  It is classified with its own multiplicity first,
+ *     so at the destination without an extra it reads as the flow above
+ *     (rate0 = +inf); anywhere else its rate0 is 0.0, the preset, since no
+ *     filling ever counts it.
+ *   - Every other flow is in flight.
+ * Epoch j = 0, 1, ...:
+ *   1. Fill.  sdnr_ecmp_fair_rates' filling over the flows in flight, steps 1-5
+ *      and the closing step 2, unchanged and in the same operation order,
+ *      kFairTie included: rate[i], the epoch's used[e] and its round count.
+ *      rate0 is the rate of epoch 0 (with max_epochs == 0 no filling runs and
+ *      the flows in flight keep rate0 = 0.0).
+ *   2. Advance.  q[i] = rem_b[i] / rate[i]; dt = min q over the flows in
+ *      flight; bound = dt + dt * kFairTie, the multiply and the add rounded one
+ *      by one (step 4's rule); t_j = t_{j-1} + dt; carried[e] += used[e] * dt,
+ *      the multiply and the add each rounded on their own (no FMA).  A flow
+ *      finishes iff q[i] <= bound, or rem_b[i] - rate[i] * dt <= 0.0 with the
+ *      multiply and the subtract rounded separately: it gets time = t_j, epoch
+ *      = j, remaining = 0 and leaves.  Otherwise rem_b[i] becomes that
+ *      difference.
+ *   3. End when nothing is in flight.  Every epoch removes a flow, so there are
+ *      at most as many epochs as flows.
+ * The epoch cap, max_epochs, epoch = -2, remaining, nepochs, epoch_time and
+ * epoch_rounds are as in sdnr_fair_times.
+ * Why the advance shares the tolerance.  Under ECMP a[e] is a float sum whose
+ * adds arrive in any order, so the levels of the device and of the restatement
+ * differ in their last bits, and with them the q of flows that end together as
+ * fractions.  With sdnr_fair_times' exact q == dt every such pair of flows would
+ * leave in one epoch on one side and in two on the other, and each spurious
+ * epoch costs a full refill with its DAG sweeps.  With the tolerance the
+ * membership of an epoch flips only at q ~ dt * (1 + 2^-30), not at every exact
+ * tie: the statement sdnr_ecmp_fair_rates makes for its levels.  The
+ * consequence for carried: a flow that leaves within the tolerance has sent at
+ * least rem_b / (1 + 2^-30), so carried[e] may fall short of the sum of mult *
+ * bytes * phi(e) over the finished flows by at most 2^-30 relative, and exceeds
+ * it only by rounding.
+ *   time, epoch, rate0, remaining [npairs], epoch_time, epoch_rounds
+ *   [max_epochs], carried [E + nextra], nepochs (HOST): as in sdnr_fair_times.
+ *   There is no bottleneck output.
+ * Device pointers only (flags must hold SDNR_DEVICE_PTRS), on the primary
+ * device of a multi-device context.  No grid-wide barrier: sdnr_fair_times'
+ * clock in device memory (phase, epoch, round) tells every queued launch what
+ * to do, and the last workgroup of an entry pass advances it.  A step is two
+ * launches on the context's stream (a row kernel in sdnr_ecmp_fair_rates' shape
+ * -- sdnr_last_kernel names its form, "ecmp_fair_times_rows_kernel<lds>" or
+ * "ecmp_fair_times_rows_kernel<global>" -- and a kernel over the E + nextra
+ * entries); the steps of an epoch, the batches of 16 behind the clock's 16
+ * bytes and sdnr_last_launches = 1 + 32 * ceil(S / 16) are those of
+ * sdnr_fair_times.  SDNR_TIMING as there.  nrows == 0 or no pairs: SDNR_OK,
+ * *nepochs = 0, nothing else touched.  pair_off[0] > pair_off[nrows] is
+ * SDNR_ERR_INVAL at once.  A row that is not a least-cost labelling of the
+ * graph under the costs in force (its flows are absent), offsets of a row
+ * outside the pair list, a capacity that is not positive and finite (taken as
+ * +inf), an extra outside [E, E + nextra) (ignored) and a byte size that is
+ * negative or not finite (that flow is absent) are reported by
+ * sdnr_synchronize as SDNR_ERR_INVAL; the other rows' flows are what they are
+ * without such a row. */
+int sdnr_ecmp_fair_times(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrows,
+                         const int64_t *pair_off, const int32_t *srcs, const uint64_t *mult,
+                         const double *bytes, const int32_t *extra /* [npairs][2] or NULL */,
+                         const double *cap, int32_t nextra, double *time, int32_t *epoch,
+                         double *rate0, double *remaining,
+                         double *epoch_time /* [max_epochs] */,
+                         int32_t *epoch_rounds /* [max_epochs] */, int32_t max_epochs,
+                         double *carried /* [E + nextra] */, int32_t *nepochs /* host */,
+                         uint32_t flags);
+
 /* Flood ports (TopologyManager._is_edge_port / _do_broadcast, reference
  * sdnmpi/topology.py:150-177): is_edge[i] = 1 iff ports[i] is neither end of
  * any link.  Keys are (dense switch id << 32) | port_no; ends (both ends of
@@ -1045,7 +1128,8 @@ int sdnr_last_launches(const sdnr_ctx *ctx, int32_t *launches);
  * kernels of sdnr_link_loads, sdnr_ecmp_link_loads, sdnr_cost_ecmp_link_loads,
  * sdnr_cost_tables, sdnr_widest_tables, sdnr_failure_ecmp_link_loads,
  * sdnr_whatif_ecmp_link_loads, sdnr_lfa_tables, sdnr_fair_rates,
- * sdnr_ecmp_fair_rates, sdnr_fair_times (their row kernel), sdnr_multicast_trees,
+ * sdnr_ecmp_fair_rates, sdnr_fair_times, sdnr_ecmp_fair_times (their row
+ * kernel), sdnr_multicast_trees,
  * sdnr_frr_link_loads (its item kernel, over the affected items) and
  * sdnr_ecmp_counts give every workgroup the rows (batches, items, groups) r,
  * r + grid, r + 2 * grid, ...: with more units of work than this a workgroup

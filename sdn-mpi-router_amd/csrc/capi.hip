@@ -122,6 +122,13 @@ int sdnr_check_watchdog(sdnr_ctx *ctx)
                              "flows read 0), pair_off outside the pair list, a capacity that is "
                              "not a positive finite number or an extra outside [E, E + nextra): "
                              "rates invalid");
+        if (h & kErrEcmpFairTimes)
+            return sdnr_fail(SDNR_ERR_INVAL, "sdnr_ecmp_fair_times: a pcost row is not a "
+                             "least-cost labelling of the uploaded graph under the costs in force "
+                             "(that row's flows are absent), pair_off outside the pair list, a "
+                             "capacity that is not a positive finite number, an extra outside "
+                             "[E, E + nextra) or a byte size that is negative or not finite (that "
+                             "flow is absent): times invalid");
         if (h & kErrCostTables)
             return sdnr_fail(SDNR_ERR_INVAL, "sdnr_cost_tables: V relaxation sweeps did not reach "
                              "the fixed point (link costs outside what sdnr_graph_costs accepts): "
@@ -1605,6 +1612,40 @@ int sdnr_ecmp_fair_rates(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrows,
     ctx->timed = (flags & SDNR_TIMING) != 0;
     return sdnr_launch_ecmp_fair_rates(ctx, pcost, nrows, pair_off, lo, hi, srcs, mult, extra, cap,
                                        nextra, rate, bott, round, level, max_rounds, used, nrounds,
+                                       (flags & SDNR_LOADS_SPLIT_HOP) != 0);
+}
+
+int sdnr_ecmp_fair_times(sdnr_ctx *ctx, const uint32_t *pcost, int32_t nrows,
+                         const int64_t *pair_off, const int32_t *srcs, const uint64_t *mult,
+                         const double *bytes, const int32_t *extra, const double *cap,
+                         int32_t nextra, double *time, int32_t *epoch, double *rate0,
+                         double *remaining, double *epoch_time, int32_t *epoch_rounds,
+                         int32_t max_epochs, double *carried, int32_t *nepochs, uint32_t flags)
+{
+    static const char name[] = "sdnr_ecmp_fair_times";
+    CHECK_CTX(ctx);
+    if (!nepochs) return sdnr_fail(SDNR_ERR_INVAL, "%s: null nepochs", name);
+    *nepochs = 0;
+    int rc = open_pair_call(ctx, flags, nrows < 0 || nextra < 0 || max_epochs < 0, name);
+    if (rc) return rc;
+    if ((int64_t)ctx->E + nextra > 0x7FFFFFFF)
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: E + nextra = %lld is no int32", name,
+                         (long long)ctx->E + nextra);
+    if (nrows == 0) return SDNR_OK;
+    if (!pcost || !pair_off) return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
+    SDNR_HIP(hipSetDevice(ctx->device));
+    int64_t lo, hi;
+    bool empty;
+    if ((rc = list_bounds(ctx, pair_off, nrows, name, "pair_off", &lo, &hi, &empty))) return rc;
+    if (empty) return SDNR_OK;
+    if (!srcs || !bytes || !time || !epoch || !rate0 || !remaining ||
+        ((!epoch_time || !epoch_rounds) && max_epochs > 0) ||
+        ((!cap || !carried) && ctx->E + nextra > 0))
+        return sdnr_fail(SDNR_ERR_INVAL, "%s: null pointer", name);
+    ctx->timed = (flags & SDNR_TIMING) != 0;
+    return sdnr_launch_ecmp_fair_times(ctx, pcost, nrows, pair_off, lo, hi, srcs, mult, bytes,
+                                       extra, cap, nextra, time, epoch, rate0, remaining,
+                                       epoch_time, epoch_rounds, max_epochs, carried, nepochs,
                                        (flags & SDNR_LOADS_SPLIT_HOP) != 0);
 }
 

@@ -359,6 +359,7 @@ static_assert(kFairLdsMaxV == 6800 && kFairLdsMaxV < 0xFFFF, "ancestors in LDS a
 constexpr int kErrFairTimes = 16777216; // sdnr_fair_times: sdnr_fair_rates' row, offset, capacity and extra errors, or a byte size that is negative or not finite
 
 constexpr int kErrEcmpFairRates = 2097152; // sdnr_ecmp_fair_rates: a pcost row is no least-cost labelling / bad offsets / a bad capacity or extra
+constexpr int kErrEcmpFairTimes = 33554432; // sdnr_ecmp_fair_times: sdnr_ecmp_fair_rates' row, offset, capacity and extra errors, or a byte size that is negative or not finite
 
 // sdnr_ecmp_fair_rates keeps a row's route counts, flows (the saturated-link
 // search aliases them), costs and depths in LDS (f64 + f64 + u32 + u16: 22
@@ -541,6 +542,16 @@ int sdnr_launch_ecmp_fair_rates(sdnr_ctx *ctx, const uint32_t *d_pcost, int32_t 
                                 const int32_t *d_extra, const double *d_cap, int32_t nextra,
                                 double *d_rate, int32_t *d_bott, int32_t *d_round, double *d_level,
                                 int32_t max_rounds, double *d_used, int32_t *nrounds, bool hop);
+// max-min fair completion times of flows split over every least-cost route
+// (ecmp_fair_times.hip); waits for the epochs and writes *nepochs
+int sdnr_launch_ecmp_fair_times(sdnr_ctx *ctx, const uint32_t *d_pcost, int32_t nrows,
+                                const int64_t *d_pair_off, int64_t pair_lo, int64_t pair_hi,
+                                const int32_t *d_srcs, const uint64_t *d_mult,
+                                const double *d_bytes, const int32_t *d_extra, const double *d_cap,
+                                int32_t nextra, double *d_time, int32_t *d_epoch, double *d_rate0,
+                                double *d_remaining, double *d_epoch_time,
+                                int32_t *d_epoch_rounds, int32_t max_epochs, double *d_carried,
+                                int32_t *nepochs, bool hop);
 // multicast trees of groups of members over tree / next-hop rows (multicast.hip);
 // mem_lo / mem_hi = mem_off[0] / mem_off[ngroups], ent_lo / ent_hi likewise of ent_off
 int sdnr_launch_multicast_trees(sdnr_ctx *ctx, const void *d_tree, int32_t layout, bool to_root,

@@ -56,110 +56,12 @@
 // The adds into a[e] arrive in any order: results equal the host restatement
 // (engine.ecmp_fair_rates_host) within rounding, and bit for bit where every
 // partial sum is exact.
-#include "common.h"
+//
+// The row pass, the link step and the launch shape live in ecmp_fair_rows.h,
+// which ecmp_fair_times.hip (a filling per departure epoch) runs too.
+#include "ecmp_fair_rows.h"
 
 namespace {
-
-constexpr int kEcmpFairThreads = 1024;   // chains of dependent LDS / L2 reads, as cost_ecmp_loads.hip
-constexpr int kEcmpFairLinkThreads = 256;
-constexpr int kFairBatch = 16;           // rounds queued per status read-back
-constexpr int kFairAlive = -2;           // round[] of a flow not frozen yet
-constexpr double kFairTie = 0x1p-30;     // shares within r_k * kFairTie of r_k tie with it
-constexpr unsigned long long kInfBits = 0x7FF0000000000000ull;
-constexpr uint32_t kEfInf = SDNR_COST_INF;
-constexpr int kNoLink = 0x7FFFFFFF;      // B[x]: no saturated link below x
-
-struct EcmpFairState {
-    double *a;                    // [E + nextra] counts of the running round (zero between rounds)
-    double *a_prev;               // [E + nextra] counts of the round before
-    double *rem;                  // [E + nextra] capacity left
-    double *share;                // [E + nextra] rem / a of the last link pass
-    double *used;                 // [E + nextra] the caller's
-    unsigned long long *level;    // [max_rounds + 1] bits of r_k, +inf until round k ran
-    long long *alive_row;         // [nrows] alive flows of a row
-    unsigned long long *status;   // 0: running, k + 1: r_k was +inf
-    unsigned int *ticket;         // workgroups of the running link pass that are done
-};
-
-// words in scratch are written by other waves of the workgroup (plain or L2
-// atomics): agent-scope accesses read past L1
-template <bool LDS>
-__device__ __forceinline__ double ef_ld_f64(const double *p)
-{
-    if (LDS) return *p;
-    return __longlong_as_double((long long)__hip_atomic_load(
-        reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED,
-        __HIP_MEMORY_SCOPE_AGENT));
-}
-
-template <bool LDS>
-__device__ __forceinline__ void ef_st_f64(double *p, double v)
-{
-    if (LDS)
-        *p = v;
-    else
-        __hip_atomic_store(reinterpret_cast<unsigned long long *>(p),
-                           (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <bool LDS>
-__device__ __forceinline__ int ef_ld_i32(const int *p)
-{
-    return LDS ? *p : __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <bool LDS>
-__device__ __forceinline__ void ef_st_i32(int *p, int v)
-{
-    if (LDS)
-        *p = v;
-    else
-        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// depth words: u16 in LDS (a depth is < V <= kEcmpFairLdsMaxV), u32 in scratch;
-// kPending (above every sweep number) marks a vertex that is not final yet
-template <bool LDS>
-struct EfDepth;
-template <>
-struct EfDepth<true> {
-    typedef uint16_t T;
-    static constexpr int kPending = 0xFFFF;
-    static __device__ __forceinline__ int ld(const T *p) { return (int)*p; }
-    static __device__ __forceinline__ void st(T *p, int v) { *p = (T)v; }
-};
-template <>
-struct EfDepth<false> {
-    typedef uint32_t T;
-    static constexpr int kPending = 0x7FFFFFFF;
-    static __device__ __forceinline__ int ld(const T *p)
-    {
-        return (int)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    static __device__ __forceinline__ void st(T *p, int v)
-    {
-        __hip_atomic_store(p, (T)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-};
-
-// the largest share that ties with the level r: r + r * kFairTie, the multiply
-// and the add rounded one by one as the host's numpy does
-__device__ __forceinline__ double ef_tie_bound(double r)
-{
-#pragma clang fp contract(off)
-    const double t = r * kFairTie;
-    return r + t;
-}
-
-// an extra constraint's index, -1 for none or for one outside [E, E + nextra)
-__device__ __forceinline__ int ef_extra(const int32_t *__restrict__ extra, int64_t i, int j, int E,
-                                        int nextra)
-{
-    if (!extra) return -1;
-    const int x = extra[2 * i + j];
-    return (x >= E && (int64_t)x < (int64_t)E + nextra) ? x : -1;
-}
 
 __global__ __launch_bounds__(kEcmpFairLinkThreads) void ecmp_fair_init_kernel(
     EcmpFairState s, const double *__restrict__ cap, int n_ent, int nlevel, int *__restrict__ err)
@@ -184,8 +86,7 @@ __global__ __launch_bounds__(kEcmpFairLinkThreads) void ecmp_fair_init_kernel(
     }
 }
 
-// hop: sigma[x] holds the number of next hops instead of the route count;
-// cost NULL: every link costs 1
+// the body is ecmp_fair_rows.h's, which sdnr_ecmp_fair_times runs too
 template <bool LDS>
 __global__ __launch_bounds__(kEcmpFairThreads) void ecmp_fair_rows_kernel(
     int V, int E, int nextra, int nrows, int hop, int k, const int32_t *__restrict__ row_ptr,
@@ -196,261 +97,28 @@ __global__ __launch_bounds__(kEcmpFairThreads) void ecmp_fair_rows_kernel(
     int32_t *__restrict__ bott, int32_t *__restrict__ round, unsigned char *__restrict__ scratch,
     size_t scratch_stride, int *__restrict__ err)
 {
-    typedef EfDepth<LDS> Dp;
-    typedef typename Dp::T depth_t;
-    // dynamic LDS, LDS form: sigma f64 [V] | flow f64 [V] | pcost u32 [V] | depth u16 [V]
     extern __shared__ __attribute__((aligned(16))) unsigned char ecmp_fair_lds[];
     __shared__ unsigned long long s_alive;
     if (k > 0 && *s.status) return;                        // the rounds ended before this one
-    const double inf = __longlong_as_double((long long)kInfBits);
-    const double r_prev = k > 0 ? __longlong_as_double((long long)s.level[k - 1]) : 0.0;
-    const double tie = ef_tie_bound(r_prev);
-    unsigned char *base = LDS ? ecmp_fair_lds : scratch + (size_t)blockIdx.x * scratch_stride;
-    double *sigma = reinterpret_cast<double *>(base);
-    double *flow = sigma + V;
-    int *B = reinterpret_cast<int *>(flow);                // dead before (b) seeds flow
-    // LDS: flow | pcost | depth; scratch: flow | depth
-    uint32_t *pc_lds = reinterpret_cast<uint32_t *>(flow + V);
-    depth_t *depth = LDS ? reinterpret_cast<depth_t *>(pc_lds + V)
-                         : reinterpret_cast<depth_t *>(flow + V);
-    const int tid = (int)threadIdx.x;
-
-    for (int r = (int)blockIdx.x; r < nrows; r += (int)gridDim.x) {
-        const int64_t lo = pair_off[r], hi = pair_off[r + 1];
-        if (lo < pair_lo || hi > pair_hi || hi < lo) {     // offsets outside the pair list
-            if (tid == 0) atomicOr(err, kErrEcmpFairRates);
-            continue;
-        }
-        if (lo == hi) continue;                            // (uniform: the row has no flow)
-        if (k > 0 && s.alive_row[r] == 0) continue;        // (uniform: none of them alive)
-        const uint32_t *prow = pcost + (size_t)r * (size_t)V;
-        const uint32_t *pc = LDS ? pc_lds : prow;
-
-        // 1. the destination (pcost 0) and the unreachable are final at depth 0
-        for (int x = tid; x < V; x += kEcmpFairThreads) {
-            const uint32_t px = prow[x];
-            if (LDS) pc_lds[x] = px;
-            ef_st_f64<LDS>(&sigma[x], (px == 0 && !hop) ? 1.0 : 0.0);
-            Dp::st(&depth[x], (px == 0 || px == kEfInf) ? 0 : Dp::kPending);
-        }
-        if (tid == 0) s_alive = 0;
-        __syncthreads();
-
-        // 2. depth and sigma: sweep j finalises the vertices whose longest chain is j
-        //    (hop split: sigma = the number of next hops)
-        bool bad = false, done = false;
-        int top = 0;
-        for (int j = 1; j <= V; ++j) {
-            int pending = 0;
-            for (int x = tid; x < V; x += kEcmpFairThreads) {
-                if (Dp::ld(&depth[x]) != Dp::kPending) continue;
-                const uint32_t px = pc[x];
-                double c = 0.0;
-                bool any = false, ready = true;
-                const int re = row_ptr[x + 1];
-                for (int e = row_ptr[x]; e < re; ++e) {
-                    const int n = col[e];
-                    const uint32_t pn = pc[n];
-                    // (64-bit sum: a row that is no labelling must not wrap into a tie)
-                    if (pn == kEfInf || (uint64_t)pn + (cost ? cost[e] : 1u) != (uint64_t)px)
-                        continue;
-                    if (Dp::ld(&depth[n]) >= j) {          // pending, or finalised in this sweep
-                        ready = false;
-                        break;
-                    }
-                    any = true;
-                    c += hop ? 1.0 : ef_ld_f64<LDS>(&sigma[n]);
-                }
-                if (!ready) {
-                    pending = 1;
-                    continue;
-                }
-                // no next hop (a finite pcost > 0 that no link explains), dead next hops, overflow
-                if (!(c > 0.0) || c > 1.7976931348623157e308) {
-                    bad = true;
-                    c = 0.0;
-                }
-                ef_st_f64<LDS>(&sigma[x], c);
-                Dp::st(&depth[x], any ? j : 0);
-            }
-            top = j;
-            if (!__syncthreads_or(pending)) {
-                done = true;
-                break;
-            }
-        }
-        if (!done) bad = true;                             // (uniform) no DAG of V vertices does that
-        // (only round 0 can find a bad row: later rounds skip it.  Its flows
-        // stay 0.0 / -1 / -1 and it contributes nothing)
-        if (k == 0 && __syncthreads_or(bad ? 1 : 0)) {
-            if (tid == 0) {
-                atomicOr(err, kErrEcmpFairRates);
-                s.alive_row[r] = 0;
-            }
-            continue;
-        }
-
-        unsigned long long mine = 0;                       // this thread's flows still alive
-        if (k == 0) {
-            // classify the row's flows (rate 0.0, bott -1, round -1 are preset)
-            for (int64_t i = lo + tid; i < hi; i += kEcmpFairThreads) {
-                const int x = srcs[i];
-                if (x < 0 || x >= V) continue;
-                if (mult && mult[i] == 0) continue;        // absent
-                const uint32_t px = pc[x];
-                if (px == kEfInf) continue;                // unreachable
-                if (extra) {
-                    const int x0 = extra[2 * i], x1 = extra[2 * i + 1];
-                    if ((x0 != -1 && ef_extra(extra, i, 0, E, nextra) < 0) ||
-                        (x1 != -1 && ef_extra(extra, i, 1, E, nextra) < 0))
-                        atomicOr(err, kErrEcmpFairRates);  // (that constraint is ignored)
-                }
-                if (px == 0 && ef_extra(extra, i, 0, E, nextra) < 0 &&
-                    ef_extra(extra, i, 1, E, nextra) < 0) {
-                    rate[i] = inf;                         // s == d and no extra
-                    continue;
-                }
-                round[i] = kFairAlive;
-                ++mine;
-            }
-        } else {
-            // (a) the verdict of round k - 1: the smallest saturated link below every vertex
-            for (int x = tid; x < V; x += kEcmpFairThreads)
-                if (Dp::ld(&depth[x]) == 0) ef_st_i32<LDS>(&B[x], kNoLink);
-            __syncthreads();
-            for (int D = 1; D <= top; ++D) {
-                for (int x = tid; x < V; x += kEcmpFairThreads) {
-                    if (Dp::ld(&depth[x]) != D) continue;
-                    const uint32_t px = pc[x];
-                    int b = kNoLink;
-                    const int re = row_ptr[x + 1];
-                    for (int e = row_ptr[x]; e < re; ++e) {
-                        const int n = col[e];
-                        const uint32_t pn = pc[n];
-                        if (pn == kEfInf || (uint64_t)pn + (cost ? cost[e] : 1u) != (uint64_t)px)
-                            continue;
-                        if (e < b && s.share[e] <= tie) b = e;
-                        const int bn = ef_ld_i32<LDS>(&B[n]);   // (depth[n] < D: final)
-                        b = bn < b ? bn : b;
-                    }
-                    ef_st_i32<LDS>(&B[x], b);
-                }
-                __syncthreads();
-            }
-            for (int64_t i = lo + tid; i < hi; i += kEcmpFairThreads) {
-                if (round[i] != kFairAlive) continue;
-                int b = ef_ld_i32<LDS>(&B[srcs[i]]);
-                if (b == kNoLink) {
-                    const int x0 = ef_extra(extra, i, 0, E, nextra);
-                    const int x1 = ef_extra(extra, i, 1, E, nextra);
-                    if (x0 >= 0 && s.share[x0] <= tie) b = x0;
-                    else if (x1 >= 0 && s.share[x1] <= tie) b = x1;
-                }
-                if (b != kNoLink) {
-                    rate[i] = r_prev;
-                    bott[i] = b;
-                    round[i] = k - 1;
-                } else {
-                    ++mine;
-                }
-            }
-        }
-        if (mine) atomicAdd(&s_alive, mine);
-        __syncthreads();                                   // (B is read; flow may be seeded)
-        const unsigned long long alive = s_alive;
-        if (tid == 0) s.alive_row[r] = (long long)alive;
-        if (alive == 0) {
-            __syncthreads();                               // s_alive is reset by the next row
-            continue;
-        }
-
-        // (b) the counts of round k: the alive multiplicities enter at their sources
-        for (int x = tid; x < V; x += kEcmpFairThreads) ef_st_f64<LDS>(&flow[x], 0.0);
-        __syncthreads();
-        for (int64_t i = lo + tid; i < hi; i += kEcmpFairThreads) {
-            if (round[i] != kFairAlive) continue;
-            const double w = (double)(mult ? mult[i] : 1ull);
-            const int x = srcs[i];
-            if (pc[x] != 0) atomicAdd(&flow[x], w);        // (s == d: only its extras count)
-            const int x0 = ef_extra(extra, i, 0, E, nextra);
-            const int x1 = ef_extra(extra, i, 1, E, nextra);
-            if (x0 >= 0) atomicAdd(&s.a[x0], w);
-            if (x1 >= 0 && x1 != x0) atomicAdd(&s.a[x1], w);
-        }
-        __syncthreads();
-        // ... and are pushed down the DAG, deepest first
-        for (int D = top; D >= 1; --D) {
-            for (int x = tid; x < V; x += kEcmpFairThreads) {
-                if (Dp::ld(&depth[x]) != D) continue;
-                const double f = ef_ld_f64<LDS>(&flow[x]);
-                const double sx = ef_ld_f64<LDS>(&sigma[x]);
-                if (!(f > 0.0) || !(sx > 0.0)) continue;
-                const uint32_t px = pc[x];
-                const int re = row_ptr[x + 1];
-                for (int e = row_ptr[x]; e < re; ++e) {
-                    const int n = col[e];
-                    const uint32_t pn = pc[n];
-                    if (pn == kEfInf || (uint64_t)pn + (cost ? cost[e] : 1u) != (uint64_t)px)
-                        continue;
-                    // sigma[n] <= sigma[x]: the share is in [0, 1]
-                    const double g = hop ? f / sx : f * (ef_ld_f64<LDS>(&sigma[n]) / sx);
-                    if (!(g > 0.0)) continue;
-                    if (pn != 0) atomicAdd(&flow[n], g);   // (pcost 0: the destination absorbs)
-                    atomicAdd(&s.a[e], g);
-                }
-            }
-            __syncthreads();
-        }
-    }
+    const FairTimes none{};
+    ecmp_fair_rows_body<LDS, false>(V, E, nextra, nrows, hop, k, row_ptr, col, cost, pcost,
+                                    pair_off, pair_lo, pair_hi, srcs, mult, extra, s, rate, bott,
+                                    round, scratch, scratch_stride, err, kErrEcmpFairRates, none,
+                                    nullptr, ecmp_fair_lds, &s_alive);
 }
 
 __global__ __launch_bounds__(kEcmpFairLinkThreads) void ecmp_fair_links_kernel(EcmpFairState s,
                                                                              int n_ent, int k)
 {
-    // the subtract, the multiply, the add and the subtract of step 2 round one
-    // by one, as the host's numpy does: no fused multiply-add
-#pragma clang fp contract(off)
     if (k > 0 && *s.status) return;                        // the rounds ended before this one
-    const double inf = __longlong_as_double((long long)kInfBits);
-    const int e = (int)(blockIdx.x * (unsigned)kEcmpFairLinkThreads + threadIdx.x);
-    double sh = inf;
-    if (e < n_ent) {
-        const double cnt = s.a[e];
-        double rem = s.rem[e];
-        if (k > 0) {
-            const double m = fmax(s.a_prev[e] - cnt, 0.0);
-            if (m > 0.0) {
-                const double r_prev = __longlong_as_double((long long)s.level[k - 1]);
-                const double p = r_prev * m;
-                s.used[e] = s.used[e] + p;
-                rem = fmax(rem - p, 0.0);
-                s.rem[e] = rem;
-            }
-        }
-        if (cnt > 0.0) sh = rem / cnt;
-        s.share[e] = sh;
-        s.a_prev[e] = cnt;
-        s.a[e] = 0.0;
-    }
-    // rem >= 0 and cnt > 0: sh is a non-negative double or +inf, ordered as its bits
-    unsigned long long bits = (unsigned long long)__double_as_longlong(sh);
-    for (int d = SDNR_WAVE / 2; d > 0; d >>= 1) {
-        const unsigned long long o = __shfl_xor(bits, d, SDNR_WAVE);
-        bits = o < bits ? o : bits;
-    }
-    if (lane_id() == 0 && bits != kInfBits) atomicMin(&s.level[k], bits);
+    ecmp_fair_links_step(s, n_ent, k);
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence();
         if (atomicAdd(s.ticket, 1u) == gridDim.x - 1) {    // the last workgroup of the pass
             __threadfence();
             *s.ticket = 0;
-            const unsigned long long lv =
-                __hip_atomic_load(&s.level[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (lv == kInfBits)
-                *s.status = (unsigned long long)k + 1;
-            else if (k > 0 && lv < s.level[k - 1])         // r_k = max(min share, r_{k-1})
-                s.level[k] = s.level[k - 1];
+            if (ecmp_fair_close_level(s, k)) *s.status = (unsigned long long)k + 1;
         }
     }
 }
@@ -470,20 +138,10 @@ int sdnr_launch_ecmp_fair_rates(sdnr_ctx *ctx, const uint32_t *d_pcost, int32_t 
     const uint32_t *cost = ctx->has_cost ? ctx->cost : nullptr;   // none: every link costs 1
 
     // the row kernel's shape, and its per-workgroup scratch slices
-    const bool lds_form = V <= kEcmpFairLdsMaxV;
-    const size_t lds = lds_form ? (((size_t)V * kEcmpFairBytesPerV + 15) & ~(size_t)15) : 0;
-    const size_t stride = lds_form ? 0 : ((((size_t)V * 20) + 255) & ~(size_t)255);
-    int64_t g;
-    if (lds_form) {
-        int per_cu = (int)(SDNR_LDS_PER_CU / (lds ? lds : 1));
-        per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);     // 2048 threads per CU
-        g = (int64_t)ctx->num_cus * per_cu;
-    } else {
-        g = (int64_t)ctx->num_cus * 2;
-        const int64_t fit = (int64_t)(kLoadsScratchBytes / stride);
-        if (g > fit) g = fit < 1 ? 1 : fit;
-    }
-    if (g > nrows) g = nrows;
+    const EcmpFairShape shape = ecmp_fair_shape(ctx, nrows);
+    const bool lds_form = shape.lds_form;
+    const size_t lds = shape.lds, stride = shape.stride;
+    const int64_t g = shape.grid;
 
     // the state behind the slices: a, a_prev, rem, share, level, alive_row, status, ticket
     const size_t slices = (stride * (size_t)g + 255) & ~(size_t)255;

@@ -3,18 +3,17 @@
 // (a filling per epoch, the round and the epoch come from device memory).  The
 // definition and the shape of the two kernels are stated in fair_rates.hip;
 // what fair_times.hip adds is marked TIMES here and compiles away without it.
+// The constants, FairTimes, the clock and the TIMES helpers that the multipath
+// forms (ecmp_fair_rows.h) share are in fair_epochs.h.
 #ifndef SDNR_FAIR_ROWS_H
 #define SDNR_FAIR_ROWS_H
 
-#include "common.h"
+#include "fair_epochs.h"
 
 namespace {
 
 constexpr int kFairThreads = 512;
 constexpr int kFairLinkThreads = 256;
-constexpr int kFairBatch = 16;           // rounds queued per status read-back
-constexpr int kFairAlive = -2;           // round[] of a flow not frozen yet
-constexpr unsigned long long kInfBits = 0x7FF0000000000000ull;
 
 struct FairRows {
     const uint32_t *tree;     // [nrows][V]: int32 parents / next hops, port16 or slot words
@@ -32,23 +31,6 @@ struct FairState {
     long long *alive_row;         // [nrows] alive flows of a row
     unsigned long long *status;   // 0: running, k + 1: r_k was +inf
     unsigned int *ticket;         // workgroups of the running link pass that are done
-};
-
-// TIMES: what a flow of sdnr_fair_times carries beside its rate and round.
-// round[] there is kFairAlive (in flight, not frozen in this epoch's filling),
-// >= 0 (in flight, frozen) or -1 (not in flight: absent, at the root, without
-// bytes, or finished).
-struct FairTimes {
-    const double *bytes;          // [npairs] the caller's
-    double *remaining;            // [npairs] rem_b, the caller's
-    double *time;                 // [npairs] the caller's, preset +inf
-    int32_t *epoch;               // [npairs] the caller's, preset -1
-    double *rate0;                // [npairs] the caller's, preset 0.0
-    long long *inflight_row;      // [nrows] flows of a row in flight
-    int j;                        // the running epoch
-    int max_epochs;
-    double dt;                    // j > 0: what epoch j - 1 lasted
-    double t;                     // j > 0: t_{j-1}
 };
 
 // what the tree word of v says: its parent (kFairNone: none), and whether v is
@@ -112,25 +94,6 @@ template <bool LDS>
 __device__ __forceinline__ unsigned long long fair_sum(const unsigned long long *p)
 {
     return LDS ? *p : __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// a capacity as the filling takes it: +inf (never saturates) and the error bit
-// for one that is not positive and finite
-__device__ __forceinline__ double fair_capacity(double c, int *__restrict__ err, int bit)
-{
-    if (!(c > 0.0) || __double_as_longlong(c) == (long long)kInfBits) {
-        atomicOr(err, bit);
-        c = __longlong_as_double((long long)kInfBits);
-    }
-    return c;
-}
-
-// TIMES: rem_b - rate * dt, the multiply and the subtract rounded one by one
-__device__ __forceinline__ double fair_bytes_left(double rem_b, double rate, double dt)
-{
-#pragma clang fp contract(off)
-    const double sent = rate * dt;
-    return rem_b - sent;
 }
 
 // The row pass of round k over the rows r = blockIdx.x, + gridDim.x, ...: the

@@ -44,22 +44,6 @@
 
 namespace {
 
-constexpr int kPhaseFill = 0, kPhaseAdvance = 1, kPhaseDone = 2, kPhaseCapped = 3;
-
-struct FairClock {
-    int phase, epoch, round, nepochs;   // (the four words the host reads)
-    double t;                           // t_{epoch - 1}
-    unsigned long long dt[2];           // bits of dt of epoch j in dt[j & 1], +inf until it ran
-};
-
-// carried + used * dt, the multiply and the add rounded one by one
-__device__ __forceinline__ double fair_carry(double carried, double used, double dt)
-{
-#pragma clang fp contract(off)
-    const double sent = used * dt;
-    return carried + sent;
-}
-
 __global__ __launch_bounds__(kFairLinkThreads) void fair_times_init_kernel(
     FairState s, FairClock *__restrict__ clock, FairTimes ft, const double *__restrict__ cap,
     double *__restrict__ carried, double *__restrict__ rate, int32_t *__restrict__ round,

@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables", "sdnr_whatif_ecmp_link_loads",
     "sdnr_widest_tables", "sdnr_fair_rates", "sdnr_ecmp_fair_rates", "sdnr_multicast_trees",
     "sdnr_last_grid", "sdnr_frr_link_loads", "sdnr_last_frr_items", "sdnr_fair_times",
+    "sdnr_ecmp_fair_times",
 )
 
 
@@ -130,6 +131,8 @@ def _bind(L):
                                   ctypes.POINTER(i32), u32], c_int),
         "sdnr_fair_times": ([vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp,
                              i32, vp, ctypes.POINTER(i32), u32], c_int),
+        "sdnr_ecmp_fair_times": ([vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp,
+                                  i32, vp, ctypes.POINTER(i32), u32], c_int),
         "sdnr_graph_twin_reps": ([vp, vp], c_int),
         "sdnr_last_dfs_searched": ([vp, ctypes.POINTER(i32)], c_int),
         "sdnr_last_dfs_form": ([vp, ctypes.POINTER(i32)], c_int),
@@ -762,6 +765,25 @@ class Context(object):
             self._h, _p(pcost_ptr), int(nrows), _p(pair_off_ptr), _p(srcs_ptr), _p(mult_ptr),
             _p(extra_ptr), _p(cap_ptr), int(nextra), _p(rate_ptr), _p(bott_ptr), _p(round_ptr),
             _p(level_ptr), int(max_rounds), _p(used_ptr), ctypes.byref(n), flags))
+        return n.value
+
+    def ecmp_fair_times_device(self, pcost_ptr, nrows, pair_off_ptr, srcs_ptr, mult_ptr,
+                               bytes_ptr, extra_ptr, cap_ptr, nextra, time_ptr, epoch_ptr,
+                               rate0_ptr, remaining_ptr, epoch_time_ptr, epoch_rounds_ptr,
+                               max_epochs, carried_ptr, hop=False, timing=False):
+        """Max-min fair completion times of flows split over every least-cost
+        route of [nrows][V] u32 pcost rows (sdnr_ecmp_fair_times, device
+        pointers): the outputs of ``fair_times_device`` over the flows of
+        ``ecmp_fair_rates_device``, and returns the number of epochs.
+        ``bytes_ptr``: f64 per flow; ``hop``: SDNR_LOADS_SPLIT_HOP.  Waits for
+        the epochs; errors of the rows surface in ``synchronize``."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0) | (LOADS_SPLIT_HOP if hop else 0)
+        n = ctypes.c_int32()
+        _check(self._lib.sdnr_ecmp_fair_times(
+            self._h, _p(pcost_ptr), int(nrows), _p(pair_off_ptr), _p(srcs_ptr), _p(mult_ptr),
+            _p(bytes_ptr), _p(extra_ptr), _p(cap_ptr), int(nextra), _p(time_ptr), _p(epoch_ptr),
+            _p(rate0_ptr), _p(remaining_ptr), _p(epoch_time_ptr), _p(epoch_rounds_ptr),
+            int(max_epochs), _p(carried_ptr), ctypes.byref(n), flags))
         return n.value
 
     def apsp_device(self, dist_ptr, timing=False):

@@ -53,7 +53,7 @@ __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "check_fair_flows", "FAIR_LDS_MAX_V", "FAIR_MULT_LIMIT", "ecmp_fair_rates_host",
            "ECMP_FAIR_LDS_MAX_V", "FAIR_TIE", "multicast_trees_host", "MCAST_LDS_BYTES",
            "multicast_maps_in_lds", "fair_times_host", "check_fair_bytes", "fair_times_launches",
-           "FAIR_TIMES_BATCH"]
+           "FAIR_TIMES_BATCH", "ecmp_fair_times_host"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -1221,6 +1221,93 @@ def ecmp_fair_rates_host(csr, cost, pcost, rows, srcs, mult, cap, extra=None, sp
     return rate, bott, rnd, np.asarray(level, np.float64), used
 
 
+def ecmp_fair_times_host(csr, cost, pcost, rows, srcs, mult, nbytes, cap, extra=None,
+                         split="route", max_epochs=None):
+    """numpy restatement of sdnr_ecmp_fair_times (the CPU tests' engine double
+    and the checker of ecmp_fair_times.hip): max-min fair completion times of
+    flows split over every least-cost route.  The flows of
+    ``ecmp_fair_rates_host`` each send ``nbytes[i]`` bytes (per parallel flow
+    of their multiplicity); they share max-min fairly, a flow that has sent its
+    bytes leaves, the others are refilled.  Returns the 7-tuple of
+    ``fair_times_host``: ``(time, epoch, rate0, remaining, epoch_time,
+    epoch_rounds, carried)``.
+
+    The definition is sdnroute.h's, step for step: every epoch is one
+    ``ecmp_fair_rates_host`` call with the departed flows' multiplicity set to
+    0, then ``q = rem_b / rate``, ``dt = min q``, ``bound = dt + dt *
+    FAIR_TIE``, ``carried += used * dt``, and a flow finishes iff ``q <=
+    bound`` or ``rem_b - rate * dt <= 0`` -- every operation a numpy operation
+    of its own.  The advance shares the filling's tie tolerance: the link
+    counts are float sums, so flows that end together as fractions have q's
+    that differ in their last bits, and an exact ``q == dt`` would spread them
+    over epochs that another summation order does not have.  The device
+    results are these within rounding, and bit for bit where every partial sum
+    is exact.  Special values as in ``fair_times_host`` (a flow at the
+    destination without an extra is the one at the row's root); a row that is
+    no least-cost labelling raises ValueError."""
+    E = int(csr.E)
+    rows = np.asarray(rows, np.int64).reshape(-1)
+    n = rows.shape[0]
+    mult, cap, extra_all, nextra = check_fair_flows(E, n, mult, cap, extra)
+    nbytes = check_fair_bytes(n, nbytes)
+    most = _fair_epoch_cap(n, max_epochs)
+    inf = np.float64(np.inf)
+    time = np.full(n, inf)
+    epoch = np.full(n, -1, np.int32)
+    left = nbytes.copy()
+    carried = np.zeros(E + nextra, np.float64)
+    e_time, e_rounds = [], []
+    fill = lambda m: ecmp_fair_rates_host(csr, cost, pcost, rows, srcs, m, cap, extra, split)  # noqa
+    if n == 0:
+        if split not in SPLITS:
+            raise ValueError("split must be 'route' or 'hop'")
+        return (time, epoch, np.zeros(0, np.float64), left, np.zeros(0, np.float64),
+                np.zeros(0, np.int32), carried)
+    empty = (nbytes == 0) & (mult > 0)
+    m = np.where(empty, np.uint64(0), mult)
+    rate0, _, rnd, level, used = fill(m)
+    if empty.any():
+        # a flow without bytes is classified as it is routed, then takes no share
+        r_all, _, k_all, _, _ = fill(mult)
+        rate0[empty & np.isinf(r_all)] = inf
+        time[empty & (np.isinf(r_all) | (k_all >= 0))] = 0.0
+    bare = np.isinf(rate0)
+    time[bare] = 0.0
+    left[bare] = 0.0
+    rate, t = rate0, np.float64(0.0)
+    tie = np.float64(FAIR_TIE)
+    for j in range(n + 1):
+        fl = np.nonzero(rnd >= 0)[0]                       # in flight
+        if fl.size == 0:
+            break
+        if j == most:
+            epoch[fl] = -2
+            if j == 0:
+                rate0[fl] = 0.0                            # (no filling ran)
+            break
+        q = left[fl] / rate[fl]
+        dt = q.min()
+        if not np.isfinite(dt):
+            break
+        slack = dt * tie
+        bound = dt + slack
+        t = t + dt
+        carried = carried + used * dt
+        rest = left[fl] - rate[fl] * dt
+        done = (q <= bound) | (rest <= 0.0)
+        time[fl[done]] = t
+        epoch[fl[done]] = j
+        left[fl] = np.where(done, 0.0, rest)
+        m[fl[done]] = 0
+        e_time.append(t)
+        e_rounds.append(len(level))
+        rate, _, rnd, level, used = fill(m)
+    else:
+        raise AssertionError("ecmp_fair_times_host: an epoch removed no flow")
+    return (time, epoch, rate0, left, np.asarray(e_time, np.float64),
+            np.asarray(e_rounds, np.int32), carried)
+
+
 FAILURE_LDS_MAX_V = 7100        # csrc/common.h kFailureLdsMaxV: what-if row state in LDS
 
 
@@ -2195,6 +2282,53 @@ class RouteEngine(object):
             e_rounds.data_ptr() if cap_e else 0, cap_e, carried.data_ptr() if NE else 0,
             to_root=to_root, timing=timing)
         self.ctx.synchronize()              # raises if a row was no tree
+        time, epoch, rate0, left = (_unsorted(a.cpu().numpy(), f.order)
+                                    for a in (time, epoch, rate0, left))
+        return (time, epoch, rate0, left, e_time.cpu().numpy()[:epochs],
+                e_rounds.cpu().numpy()[:epochs], carried.cpu().numpy())
+
+    def ecmp_fair_times(self, export, cost, pcost, rows, srcs, mult=None, nbytes=1.0, cap=None,
+                        extra=None, split="route", max_epochs=None, timing=False):
+        """Max-min fair completion times of flows split over every least-cost
+        route (ecmp_fair_times.hip, sdnr_ecmp_fair_times): the 7-tuple of
+        ``fair_times`` in the flows' order, what ``ecmp_fair_times_host``
+        returns within rounding (bit for bit where every partial sum is
+        exact); the epoch count, every flow's epoch and every filling's round
+        count are equal unless a decision lies within rounding of the tie
+        tolerance 2**-30.
+
+        ``cost``, ``pcost``, ``rows``, ``srcs``, ``split`` as in
+        ``ecmp_fair_rates``; ``mult``, ``nbytes``, ``cap``, ``extra`` and
+        ``max_epochs`` as in ``fair_times``.  The epochs and their fillings
+        advance on the device; the host reads one status word per batch of
+        launches."""
+        if split not in SPLITS:
+            raise ValueError("split must be 'route' or 'hop'")
+        self._use_costs(export, cost)
+        t = self._torch
+        f = self._fair_flows_device("ecmp_fair_times", export, self._pcost_device(pcost), rows,
+                                    srcs, mult, cap, extra, word=4)
+        n, NE = f.n, f.NE
+        nbytes = check_fair_bytes(n, nbytes)
+        cap_e = _fair_epoch_cap(n, max_epochs)
+        if f.order is None:
+            return (np.zeros(0, np.float64), np.zeros(0, np.int32), np.zeros(0, np.float64),
+                    np.zeros(0, np.float64), np.zeros(0, np.float64), np.zeros(0, np.int32),
+                    np.zeros(NE, np.float64))
+        d_b = t.from_numpy(np.ascontiguousarray(nbytes[f.order])).to(self.dev)
+        time, rate0, left = (t.empty(n, dtype=t.float64, device=self.dev) for _ in range(3))
+        epoch = t.empty(n, dtype=t.int32, device=self.dev)
+        e_time = t.empty(cap_e, dtype=t.float64, device=self.dev)
+        e_rounds = t.empty(cap_e, dtype=t.int32, device=self.dev)
+        carried = t.zeros(NE, dtype=t.float64, device=self.dev)
+        self._ready()
+        epochs = self.ctx.ecmp_fair_times_device(
+            f.table.data_ptr(), f.nrows, f.d_off.data_ptr(), f.d_x.data_ptr(), _ptr(f.d_m),
+            d_b.data_ptr(), _ptr(f.d_e), f.d_cap.data_ptr() if NE else 0, f.nextra,
+            time.data_ptr(), epoch.data_ptr(), rate0.data_ptr(), left.data_ptr(),
+            e_time.data_ptr() if cap_e else 0, e_rounds.data_ptr() if cap_e else 0, cap_e,
+            carried.data_ptr() if NE else 0, hop=split == "hop", timing=timing)
+        self.ctx.synchronize()              # raises if a row was no least-cost labelling
         time, epoch, rate0, left = (_unsorted(a.cpu().numpy(), f.order)
                                     for a in (time, epoch, rate0, left))
         return (time, epoch, rate0, left, e_time.cpu().numpy()[:epochs],

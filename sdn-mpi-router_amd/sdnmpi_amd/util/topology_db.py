@@ -400,10 +400,12 @@ class FlowTimes(object):
     ``epoch_rounds[j]`` the rounds of its filling, ``epochs`` their number;
     ``link_bytes`` is a :class:`SplitLinkLoads` of the bytes every link
     carried (last hops: the bytes out of every host port, when host ports are
-    modelled); ``complete`` says that no pair is still sending."""
+    modelled); ``complete`` says that no pair is still sending; ``split`` is
+    how a multipath route divided a pair ("route" for the single-path routes)."""
 
     def __init__(self, pairs, weights, nbytes, time, epoch, routed, rate0, remaining, epoch_time,
-                 epoch_rounds, link_bytes):
+                 epoch_rounds, link_bytes, split="route"):
+        self.split = split
         self.pairs = pairs
         self.weights = weights
         self.bytes = nbytes
@@ -3120,13 +3122,22 @@ class TopologyDB(object):
 
     # -- max-min fair completion times ---------------------------------------
     def _fair_times(self, ex, pairs, w, nbytes, sv, dv, ports, capacity, host_capacity, route,
-                    max_epochs):
+                    max_epochs, split="route"):
         """FlowTimes of pairs already resolved, as :meth:`_fair` takes them,
         each sending ``nbytes[i]`` bytes per flow."""
-        if route not in self.FAIR_ROUTES:
+        if split not in ("route", "hop"):
+            raise ValueError("split must be 'route' or 'hop'")
+        if route not in self.FAIR_ROUTES + self.FAIR_ECMP_ROUTES:
+            raise ValueError("route must be one of %s (got %r)" % (", ".join(
+                map(repr, self.FAIR_ROUTES + self.FAIR_ECMP_ROUTES)), route))
+        if route in self.FAIR_ECMP_ROUTES and not hasattr(self.engine, "ecmp_fair_times"):
             # (a missing kernel is an error, never a fall-back to one path per pair)
-            raise ValueError("completion times follow one path per pair: route must be one of %s "
-                             "(got %r)" % (", ".join(map(repr, self.FAIR_ROUTES)), route))
+            raise ValueError("route=%r needs an engine with ecmp_fair_times (the multipath "
+                             "epochs); this one offers only the single-path routes %s"
+                             % (route, ", ".join(map(repr, self.FAIR_ROUTES))))
+        if split != "route" and route not in self.FAIR_ECMP_ROUTES:
+            raise ValueError("split=%r needs a multipath route (%s): %r puts a pair on one path"
+                             % (split, ", ".join(map(repr, self.FAIR_ECMP_ROUTES)), route))
         n = sv.shape[0]
         E = int(ex.csr.E)
         b = np.asarray(nbytes, np.float64)
@@ -3157,21 +3168,27 @@ class TopologyDB(object):
             fs, fd = fkey[:, 0], fkey[:, 1]
             extra = fkey[:, 2:4] if host_capacity is not None else None
             fb = np.ascontiguousarray(fkey[:, -1]).view(np.float64)
-            tree, layout, rows, verts, to_root, reach = self._fair_rows(ex, route, fs, fd)
-            # (next-hop rows cannot tell an unreached vertex from the root)
-            verts = np.where(reach, verts, -1)
-            t, k, r0, rest, e_time, e_rounds, carried = self.engine.fair_times(
-                ex, tree, layout, rows, verts, fw, fb, cap, extra, to_root=to_root,
-                max_epochs=max_epochs)
+            if route in self.FAIR_ECMP_ROUTES:
+                cost, pcost, rows, reach = self._fair_ecmp_rows(ex, route, fs, fd)
+                t, k, r0, rest, e_time, e_rounds, carried = self.engine.ecmp_fair_times(
+                    ex, cost, pcost, rows, fs, fw, fb, cap, extra, split, max_epochs=max_epochs)
+            else:
+                tree, layout, rows, verts, to_root, reach = self._fair_rows(ex, route, fs, fd)
+                # (next-hop rows cannot tell an unreached vertex from the root)
+                verts = np.where(reach, verts, -1)
+                t, k, r0, rest, e_time, e_rounds, carried = self.engine.fair_times(
+                    ex, tree, layout, rows, verts, fw, fb, cap, extra, to_root=to_root,
+                    max_epochs=max_epochs)
             time[ok], epoch[ok], rate0[ok], left[ok] = t[finv], k[finv], r0[finv], rest[finv]
             routed[ok] = reach[finv]
         link_bytes = self._link_loads_result(ex, carried[:E], hkey, carried[E + nin:],
                                              SplitLinkLoads)
         return FlowTimes(pairs, w, b, time, epoch, routed, rate0, left, e_time, e_rounds,
-                         link_bytes)
+                         link_bytes, split)
 
     def fair_completion_times(self, pairs, nbytes, weights=None, capacity=None,
-                              host_capacity=None, route="default", max_epochs=None):
+                              host_capacity=None, route="default", max_epochs=None,
+                              split="route"):
         """When every (src_mac, dst_mac) pair of ``pairs`` has sent its
         ``nbytes[i]`` bytes (one number: the same for all) if all start at
         once and share the links max-min fairly throughout: a pair that is
@@ -3180,17 +3197,27 @@ class TopologyDB(object):
 
         ``weights``, ``capacity`` and ``host_capacity`` as in
         :meth:`fair_rates`; pair i stands for ``weights[i]`` parallel flows of
-        ``nbytes[i]`` bytes each.  ``route``: one of the single-path tables
-        ``"default"``, ``"shortest"``, ``"least_cost"``, ``"least_loaded"``
-        (the multipath routes are a ValueError).  ``max_epochs``: stop after
+        ``nbytes[i]`` bytes each.  ``route`` and ``split`` as in
+        :meth:`fair_rates`: one of the single-path tables ``"default"``,
+        ``"shortest"``, ``"least_cost"``, ``"least_loaded"``, or the multipath
+        sets ``"ecmp"`` and ``"least_cost_ecmp"``, which ``split`` divides by
+        ``"route"`` or ``"hop"`` (anything but ``"route"`` with a single-path
+        route is a ValueError; so is a multipath route on an engine without
+        the multipath epochs).  ``max_epochs``: stop after
         that many departure epochs; the pairs still sending read ``time`` inf,
         ``epoch`` -2 and what they have left in ``remaining``.  Byte sizes that
         are negative, NaN or inf are a ValueError.  Pairs merge into one flow
         class only when switches, host ports and bytes are equal.  The GPU
-        runs the epochs and their fillings (fair_times.hip) from state on the
-        device, bit for bit equal to ``engine.fair_times_host``; there is no
-        tie tolerance, so pairs that end together as fractions may leave one
-        ulp apart in consecutive epochs."""
+        runs the epochs and their fillings from state on the device.  Under
+        the single-path routes (fair_times.hip) the result is bit for bit
+        ``engine.fair_times_host``; there is no tie tolerance, so pairs that
+        end together as fractions may leave one ulp apart in consecutive
+        epochs.  Under the multipath routes
+        (ecmp_fair_times.hip; ``engine.ecmp_fair_times_host`` within rounding)
+        the link counts are float sums, so the advance shares the filling's
+        tolerance: a pair whose bytes would last within 2**-30 (relative) of
+        the epoch's length leaves with it, and the links then carried that
+        much less than its bytes."""
         ex = self.graph()
         pairs = list(pairs)
         n = len(pairs)
@@ -3209,21 +3236,23 @@ class TopologyDB(object):
             dport[i] = self._last_hop(eb[0], eb[1], b)[1]
         ports = (sport, dport, [a for a, _ in pairs], [b for _, b in pairs])
         return self._fair_times(ex, pairs, w, nbytes, sv, dv, ports, capacity, host_capacity,
-                                route, max_epochs)
+                                route, max_epochs, split)
 
     def all_pairs_fair_completion_times(self, nbytes=1.0, capacity=None, route="default",
-                                        max_epochs=None):
+                                        max_epochs=None, split="route"):
         """:meth:`fair_completion_times` of every ordered pair of distinct
         hosts at once, ``nbytes`` bytes each (MPI_Alltoall with equal blocks),
         in the switch-pair form of :meth:`all_pairs_fair_rates` (the MAC-pair
-        form when a host MAC names a switch)."""
+        form when a host MAC names a switch).  ``route`` and ``split`` as in
+        :meth:`fair_completion_times`."""
         if isinstance(nbytes, bool) or not isinstance(nbytes, (int, float, np.integer,
                                                                np.floating)):
             raise ValueError("nbytes is one number for every pair")
         if any(self._mac_to_int(m) in self.switches for m in self.hosts):
             macs = list(self.hosts)
             return self.fair_completion_times([(a, b) for a in macs for b in macs if a != b],
-                                              nbytes, None, capacity, None, route, max_epochs)
+                                              nbytes, None, capacity, None, route, max_epochs,
+                                              split)
         ex = self.graph()
         hv = np.asarray(self._host_vertices(ex), np.int64)
         hc = np.asarray(ex.host_count, np.int64)
@@ -3233,20 +3262,22 @@ class TopologyDB(object):
         dp = ex.csr.dpids
         pairs = list(zip(dp[sv].tolist(), dp[dv].tolist()))
         return self._fair_times(ex, pairs, w, nbytes, sv, dv, None, capacity, None, route,
-                                max_epochs)
+                                max_epochs, split)
 
     def mpi_exchange_times(self, rank_to_mac, traffic=None, capacity=None, host_capacity=None,
-                           route="default", max_epochs=None):
+                           route="default", max_epochs=None, split="route"):
         """:meth:`fair_completion_times` of an MPI job's exchange: the keys of
         ``traffic`` = {(src_rank, dst_rank): bytes} give the pairs, one flow
         each (None: every ordered rank pair i != j, one byte each).
         ``makespan()`` of the result is how long the exchange takes; it is
-        never above ``mpi_fair_rates(...).step_time()`` beyond rounding."""
+        never above ``mpi_fair_rates(...).step_time()`` beyond rounding (under
+        the multipath routes: beyond their tolerance, 2**-30 relative).
+        ``route`` and ``split`` as in :meth:`fair_completion_times`."""
         pairs, nbytes = self._rank_pairs(rank_to_mac, traffic)
         b = np.ones(len(pairs), np.float64) if nbytes is None else \
             np.asarray([float(x) for x in nbytes], np.float64).reshape(-1)
         return self.fair_completion_times(pairs, b, None, capacity, host_capacity, route,
-                                          max_epochs)
+                                          max_epochs, split)
 
     def find_routes(self, pairs, multiple=False):
         """find_route over many (src_mac, dst_mac) pairs; tables are computed
