@@ -674,6 +674,50 @@ int sdnr_lfa_tables(sdnr_ctx *ctx, const uint32_t *pcost_all, const int32_t *dst
                     int32_t *backup, int32_t *backup_port, uint8_t *kind, uint32_t *counts,
                     uint32_t flags);
 
+/* Remote loop-free alternates (RFC 7490): where no neighbour of a switch is
+ * loop-free, the packet is tunnelled to a remote PQ node that is reached
+ * without the failed link and reaches the link's far end without it.  One
+ * repair per directed link.  Integer and bit-exact.
+ *   pcost_all  [V][V] u32 as in sdnr_lfa_tables; D(a, b) = pcost_all[b][a] is
+ *              the least cost a -> b, SDNR_COST_INF: no route.  With no costs
+ *              uploaded every link costs 1;
+ *   verts      [nverts] source vertices (dense ids), or NULL: 0 .. nverts - 1;
+ *   pq, via, via_port [E] int32, tunnel_cost [E] u64, kind [E] u8, in CSR edge
+ *              order: a unit (one source vertex S) WRITES the entries of S's
+ *              out-links and touches no other; a vertex listed twice writes
+ *              the same values twice;
+ *   counts     [nverts][4] u32 or NULL: WRITTEN -- the unit's out-links that
+ *              are no self-loops, those repaired, those with kind & 2, those
+ *              with kind & 4.
+ * For a link e = (S -> E) of cost c, E != S (a self-loop gets no repair):
+ *   Q-space    X != S with D(X,E) finite and (D(X,S) INF or
+ *              D(X,E) < D(X,S) + c): no least-cost route X -> E uses e;
+ *   extended P-space through N, the head of an out-link f = (S -> N), N != E,
+ *              N != S: D(N,X) finite and (D(N,S) INF or D(E,X) INF or
+ *              D(N,X) < D(N,S) + c + D(E,X)): no least-cost route N -> X uses
+ *              e (X = N qualifies).
+ * The repair of e is the (X, N), X in the Q-space and in the extended P-space
+ * through N, of the smallest key (cost[f] + D(N,X), X, N): pq = X, via = N,
+ * via_port = f's port, tunnel_cost = cost[f] + D(N,X), kind = 1 | 2 where X is
+ * in S's own P-space (D(S,X) finite and (D(E,X) INF or D(S,X) < c + D(E,X)):
+ * the tunnel needs no directed forwarding) | 4 where X == N (a per-link
+ * loop-free alternate, no tunnel); -1 / -1 / -1 / 0 / 0 where there is none.
+ * Every sum is taken in 64 bits (three table entries may reach 3 (2^32 - 2))
+ * and INF enters none.
+ * A pre-pass transposes pcost_all into the context scratch (4 V^2 bytes; more
+ * than 1 GiB is SDNR_ERR_NOMEM), so that the main kernel streams rows only.
+ * V is at most 16,384 (sdnr_lfa_tables' cap), above it SDNR_ERR_INVAL before
+ * anything is read.  Device pointers only (flags must hold SDNR_DEVICE_PTRS);
+ * asynchronous on the context stream; on a multi-device context it runs on
+ * the primary device; SDNR_TIMING times the main kernel (not the transpose).
+ * Without an uploaded graph: SDNR_ERR_STATE.  nverts == 0: SDNR_OK, nothing
+ * touched.  A verts[i] outside [0, V) is an empty unit (counts 0, no entry
+ * written).  The table is taken as given: one that is no least-cost labelling
+ * of the graph gives the repairs these inequalities define on it. */
+int sdnr_remote_lfa(sdnr_ctx *ctx, const uint32_t *pcost_all, const int32_t *verts, int32_t nverts,
+                    int32_t *pq, int32_t *via, int32_t *via_port, uint64_t *tunnel_cost,
+                    uint8_t *kind, uint32_t *counts, uint32_t flags);
+
 /* Fast-reroute what-if: the link loads of a demand while the switches' backup
  * next hops are forwarding -- after a failure, before the controller has
  * re-routed (sdnr_failure_ecmp_link_loads is the state after that).  Integer
@@ -1129,7 +1173,7 @@ int sdnr_last_launches(const sdnr_ctx *ctx, int32_t *launches);
  * sdnr_cost_tables, sdnr_widest_tables, sdnr_failure_ecmp_link_loads,
  * sdnr_whatif_ecmp_link_loads, sdnr_lfa_tables, sdnr_fair_rates,
  * sdnr_ecmp_fair_rates, sdnr_fair_times, sdnr_ecmp_fair_times (their row
- * kernel), sdnr_multicast_trees,
+ * kernel), sdnr_multicast_trees, sdnr_remote_lfa (its units are source vertices),
  * sdnr_frr_link_loads (its item kernel, over the affected items) and
  * sdnr_ecmp_counts give every workgroup the rows (batches, items, groups) r,
  * r + grid, r + 2 * grid, ...: with more units of work than this a workgroup

@@ -1915,6 +1915,27 @@ int sdnr_lfa_tables(sdnr_ctx *ctx, const uint32_t *pcost_all, const int32_t *dst
                                   (flags & SDNR_LFA_LINK_ONLY) != 0);
 }
 
+int sdnr_remote_lfa(sdnr_ctx *ctx, const uint32_t *pcost_all, const int32_t *verts, int32_t nverts,
+                    int32_t *pq, int32_t *via, int32_t *via_port, uint64_t *tunnel_cost,
+                    uint8_t *kind, uint32_t *counts, uint32_t flags)
+{
+    CHECK_CTX(ctx);
+    if (ctx->V < 0) return sdnr_fail(SDNR_ERR_STATE, "sdnr_remote_lfa: no graph uploaded");
+    if (!(flags & SDNR_DEVICE_PTRS))
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_remote_lfa: device pointers only");
+    if (nverts < 0) return sdnr_fail(SDNR_ERR_INVAL, "sdnr_remote_lfa: negative count");
+    if (ctx->V > kLfaMaxV)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_remote_lfa: V=%d above %d (the all-pairs table)",
+                         ctx->V, kLfaMaxV);
+    if (nverts == 0 || ctx->V == 0) return SDNR_OK;
+    if (!pcost_all || !pq || !via || !via_port || !tunnel_cost || !kind)
+        return sdnr_fail(SDNR_ERR_INVAL, "sdnr_remote_lfa: null pointer");
+    SDNR_HIP(hipSetDevice(ctx->device));
+    ctx->timed = (flags & SDNR_TIMING) != 0;
+    return sdnr_launch_remote_lfa(ctx, pcost_all, verts, nverts, pq, via, via_port, tunnel_cost,
+                                  kind, counts);
+}
+
 int sdnr_widest_tables(sdnr_ctx *ctx, const uint32_t *pcost, const uint32_t *util,
                        const int32_t *dst, int32_t ndst, uint32_t *bott, int32_t *nh,
                        int32_t *nh_port, uint32_t flags)

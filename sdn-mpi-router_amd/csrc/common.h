@@ -513,6 +513,10 @@ int sdnr_launch_whatif_peak(sdnr_ctx *ctx, int32_t nscen, const double *d_load,
 int sdnr_launch_lfa_tables(sdnr_ctx *ctx, const uint32_t *d_pcost_all, const int32_t *d_dst,
                            int32_t ndst, int32_t *d_backup, int32_t *d_backup_port,
                            uint8_t *d_kind, uint32_t *d_counts, bool link_only);
+// remote loop-free alternates: a PQ-node repair tunnel per link (remote_lfa.hip)
+int sdnr_launch_remote_lfa(sdnr_ctx *ctx, const uint32_t *d_pcost_all, const int32_t *d_verts,
+                           int32_t nverts, int32_t *d_pq, int32_t *d_via, int32_t *d_via_port,
+                           uint64_t *d_tunnel_cost, uint8_t *d_kind, uint32_t *d_counts);
 // least-loaded (min-max utilisation) next hops inside the least-cost DAG (widest_tables.hip)
 int sdnr_launch_widest_tables(sdnr_ctx *ctx, const uint32_t *d_pcost, const uint32_t *d_util,
                               const int32_t *d_dst, int32_t ndst, uint32_t *d_bott, int32_t *d_nh,

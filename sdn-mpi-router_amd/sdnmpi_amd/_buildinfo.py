@@ -23,7 +23,7 @@ SOURCES = ("capi.hip", "dfs.hip", "shortest.hip", "apsp.hip", "routes.hip", "ecm
            "incremental.hip", "loads.hip", "ecmp_loads.hip", "cost_tables.hip",
            "cost_ecmp_loads.hip", "failure_loads.hip", "lfa_tables.hip", "whatif_loads.hip",
            "widest_tables.hip", "fair_rates.hip", "ecmp_fair_rates.hip", "multicast.hip",
-           "frr_loads.hip", "fair_times.hip", "ecmp_fair_times.hip")
+           "frr_loads.hip", "fair_times.hip", "ecmp_fair_times.hip", "remote_lfa.hip")
 HEADERS = (("csrc", "common.h"), ("csrc", "rowstate.h"), ("csrc", "scenario_row.h"),
            ("csrc", "fair_epochs.h"), ("csrc", "fair_rows.h"), ("csrc", "ecmp_fair_rows.h"),
            ("include", "sdnroute.h"))

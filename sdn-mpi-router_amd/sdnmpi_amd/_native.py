@@ -55,7 +55,7 @@ EXPORTED_SYMBOLS = (
     "sdnr_failure_ecmp_link_loads", "sdnr_lfa_tables", "sdnr_whatif_ecmp_link_loads",
     "sdnr_widest_tables", "sdnr_fair_rates", "sdnr_ecmp_fair_rates", "sdnr_multicast_trees",
     "sdnr_last_grid", "sdnr_frr_link_loads", "sdnr_last_frr_items", "sdnr_fair_times",
-    "sdnr_ecmp_fair_times",
+    "sdnr_ecmp_fair_times", "sdnr_remote_lfa",
 )
 
 
@@ -140,6 +140,7 @@ def _bind(L):
         "sdnr_frr_link_loads": ([vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp,
                                  u32], c_int),
         "sdnr_last_frr_items": ([vp, ctypes.POINTER(ctypes.c_int64)], c_int),
+        "sdnr_remote_lfa": ([vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, u32], c_int),
     }
     # an A/B build named by SDNROUTE_LIB may predate some entry points: those
     # stay unbound (calling one raises AttributeError); the in-tree library
@@ -631,6 +632,22 @@ class Context(object):
         _check(self._lib.sdnr_lfa_tables(
             self._h, _p(pcost_all_ptr), _p(dst_ptr), int(ndst), _p(backup_ptr), _p(backup_port_ptr),
             _p(kind_ptr), _p(counts_ptr), flags))
+
+    def remote_lfa_device(self, pcost_all_ptr, verts_ptr, nverts, pq_ptr, via_ptr, via_port_ptr,
+                          tunnel_cost_ptr, kind_ptr, counts_ptr=0, timing=False):
+        """Remote loop-free alternates of the out-links of ``nverts`` source
+        vertices (sdnr_remote_lfa, device pointers, asynchronous):
+        ``pcost_all`` u32 [V][V] as in ``lfa_tables_device``; ``verts`` int32
+        [nverts] or 0 (0 .. nverts - 1); written, in CSR edge order and only
+        at the out-links of the listed vertices: ``pq``, ``via``, ``via_port``
+        int32 [E], ``tunnel_cost`` u64 [E], ``kind`` u8 [E] (1 = a repair
+        exists, 2 = the PQ node is in the source's own P-space, 4 = it is the
+        neighbour itself) and, unless 0, ``counts`` u32 [nverts][4] (links
+        that are no self-loops, repaired, kind & 2, kind & 4)."""
+        flags = DEVICE_PTRS | (TIMING if timing else 0)
+        _check(self._lib.sdnr_remote_lfa(
+            self._h, _p(pcost_all_ptr), _p(verts_ptr), int(nverts), _p(pq_ptr), _p(via_ptr),
+            _p(via_port_ptr), _p(tunnel_cost_ptr), _p(kind_ptr), _p(counts_ptr), flags))
 
     def apsp(self):
         dist = np.empty((self.V, self.V), np.uint16)

@@ -53,7 +53,8 @@ __all__ = ["RouteEngine", "TableCache", "tree_path", "expand_tree_paths",
            "check_fair_flows", "FAIR_LDS_MAX_V", "FAIR_MULT_LIMIT", "ecmp_fair_rates_host",
            "ECMP_FAIR_LDS_MAX_V", "FAIR_TIE", "multicast_trees_host", "MCAST_LDS_BYTES",
            "multicast_maps_in_lds", "fair_times_host", "check_fair_bytes", "fair_times_launches",
-           "FAIR_TIMES_BATCH", "ecmp_fair_times_host"]
+           "FAIR_TIMES_BATCH", "ecmp_fair_times_host", "remote_lfa_host", "RLFA_REPAIR",
+           "RLFA_PLAIN", "RLFA_LFA"]
 
 # bytes of device tables one TableCache keeps per route mode before it
 # evicts rows (SDNROUTE_TABLE_BUDGET overrides); the torus 32^3 default-route
@@ -1582,6 +1583,99 @@ def lfa_tables_host(csr, cost, pcost_all, dsts, link_only=False):
     return backup, bport, kind, counts
 
 
+RLFA_REPAIR, RLFA_PLAIN, RLFA_LFA = 1, 2, 4        # bits of sdnr_remote_lfa's kind
+
+
+def remote_lfa_host(csr, cost, pcost_all, verts=None):
+    """numpy restatement of sdnr_remote_lfa (the CPU tests' engine double and
+    the checker of remote_lfa.hip): (pq, via, via_port int32 [E], tunnel_cost
+    uint64 [E], kind uint8 [E], counts uint32 [n, 4]) -- the remote loop-free
+    alternate (RFC 7490 PQ-node repair tunnel) of every out-link of the source
+    vertices ``verts`` (None: all of them, 0 .. V - 1).
+
+    ``pcost_all`` and ``cost`` as in ``lfa_tables_host``; D(a, b) =
+    pcost_all[b][a].  For a link e = (S -> E) of cost c, E != S, a vertex X != S
+    is in the Q-space iff D(X,E) is finite and (D(X,S) is INF or D(X,E) <
+    D(X,S) + c), and in the extended P-space through the head N of another
+    out-link f of S (N != E, N != S) iff D(N,X) is finite and (D(N,S) is INF or
+    D(E,X) is INF or D(N,X) < D(N,S) + c + D(E,X)).  The repair is the (X, N)
+    in both of the smallest (cost[f] + D(N,X), X, N): ``pq`` = X, ``via`` = N,
+    ``via_port`` = f's port, ``tunnel_cost`` the key's first component,
+    ``kind`` = RLFA_REPAIR | RLFA_PLAIN (X is in S's own P-space: D(S,X) finite
+    and (D(E,X) INF or D(S,X) < c + D(E,X))) | RLFA_LFA (X == N); -1 / -1 / -1
+    / 0 / 0 where there is none, and at a self-loop.  Only the out-links of the
+    listed vertices are written (the others keep -1 / -1 / -1 / 0 / 0); a vertex
+    outside [0, V) is an empty unit.  ``counts``: per unit, the out-links that
+    are no self-loops, those repaired, those RLFA_PLAIN, those RLFA_LFA.
+
+    A CSR row is strictly ascending (no two links of a vertex share a head, as
+    sdnr_graph_upload requires), so N != E excludes exactly the link's own slot.
+
+    Deliberately not the kernel's shape: per link one [deg, V] mask over every
+    (neighbour, X) at once and numpy minima for the choice; int64 throughout:
+    no sum can wrap."""
+    V, E = int(csr.V), int(csr.E)
+    cost = np.ones(E, np.uint32) if cost is None else check_link_costs(csr, cost)
+    P = _pcost_u32(pcost_all)
+    if P.shape != (V, V):
+        raise ValueError("pcost_all is the [V, V] all-pairs table (row v: destination v)")
+    verts = np.arange(V, dtype=np.int64) if verts is None else np.asarray(verts, np.int64)
+    n = int(verts.shape[0])
+    pq = np.full(E, -1, np.int32)
+    via = np.full(E, -1, np.int32)
+    vport = np.full(E, -1, np.int32)
+    tcost = np.zeros(E, np.uint64)
+    kind = np.zeros(E, np.uint8)
+    counts = np.zeros((n, 4), np.uint32)
+    rp = np.asarray(csr.row_ptr, np.int64)
+    col = np.asarray(csr.col, np.int64)
+    port = np.asarray(csr.port, np.int32)
+    INF = int(COST_INF)
+    P64 = P.astype(np.int64)
+    for u, s in enumerate(verts.tolist()):
+        if s < 0 or s >= V:
+            continue                                       # unknown vertex: an empty unit
+        lo, hi = int(rp[s]), int(rp[s + 1])
+        nb = col[lo:hi]
+        cs = cost[lo:hi].astype(np.int64)
+        DN = P64[:, nb].T                                  # [deg, V]: D(N_j, X)
+        back = P64[s, nb]                                  # D(N_j, S)
+        DS = P64[s]                                        # D(X, S)
+        tc_all = cs[:, None] + DN
+        for i in range(hi - lo):
+            e, t, c = lo + i, int(nb[i]), int(cs[i])
+            pq[e], via[e], vport[e], tcost[e], kind[e] = -1, -1, -1, 0, 0
+            if t == s:
+                continue
+            counts[u, 0] += 1
+            DE = P64[t]                                    # D(X, E)
+            q = (DE != INF) & ((DS == INF) | (DE < DS + c))
+            q[s] = False
+            dex = DN[i]                                    # D(E, X)
+            ok = (DN != INF) & ((back[:, None] == INF) | (dex[None, :] == INF) |
+                                (DN < back[:, None] + c + dex[None, :]))
+            ok &= q[None, :]
+            ok[i] = False
+            ok[nb == s] = False
+            if not ok.any():
+                continue
+            tc = np.where(ok, tc_all, np.int64(1) << 40)
+            best = int(tc.min())
+            x = int(np.nonzero((tc == best).any(axis=0))[0][0])
+            j = int(np.nonzero(tc[:, x] == best)[0][0])
+            dsx, dtx = int(P64[x, s]), int(P64[x, t])      # D(S, X), D(E, X)
+            k = RLFA_REPAIR
+            if dsx != INF and (dtx == INF or dsx < c + dtx):
+                k |= RLFA_PLAIN
+                counts[u, 2] += 1
+            if x == int(nb[j]):
+                k |= RLFA_LFA
+                counts[u, 3] += 1
+            counts[u, 1] += 1
+            pq[e], via[e], vport[e], tcost[e], kind[e] = x, int(nb[j]), port[lo + j], best, k
+    return pq, via, vport, tcost, kind, counts
+
+
 FRR_MAX_V = 6200                # csrc/common.h kFrrMaxV: the fast-reroute item state in LDS
 
 
@@ -2593,6 +2687,41 @@ class RouteEngine(object):
                                        link_only=link_only, timing=timing)
             self.ctx.synchronize()          # raises on a row that is no least-cost labelling
         return backup, bport, kind, counts.cpu().numpy().view(np.uint32)
+
+    def remote_lfa(self, export, cost, pcost_all, verts=None, timing=False):
+        """Remote loop-free alternates (remote_lfa.hip, sdnr_remote_lfa): (pq,
+        via, via_port int32 [E], tunnel_cost uint64 [E], kind uint8 [E], counts
+        uint32 [n, 4]) on the host, as ``remote_lfa_host`` defines them, for
+        the out-links of the source vertices ``verts`` (None: every vertex).
+
+        ``cost`` and ``pcost_all`` as in ``lfa_tables``.  The entries of links
+        whose source is not listed read -1 / -1 / -1 / 0 / 0; a vertex outside
+        [0, V) is an empty unit.  V above ``LFA_MAX_V`` raises."""
+        self._use_costs(export, cost)
+        t = self._torch
+        V, E = int(export.csr.V), int(export.csr.E)
+        v = np.arange(V, dtype=np.int64) if verts is None else np.asarray(verts, np.int64)
+        n = int(v.shape[0])
+        v = np.where((v < 0) | (v >= V), -1, v).astype(np.int32)
+        pcost_all = self._pcost_device(pcost_all)
+        if tuple(pcost_all.shape) != (V, V) or pcost_all.element_size() != 4:
+            raise ValueError("pcost_all is the [V, V] 4-byte all-pairs table (row v: "
+                             "destination v)")
+        pcost_all = pcost_all.contiguous()
+        i32 = t.full((3, max(E, 1)), -1, dtype=t.int32, device=self.dev)
+        tcost = t.zeros(max(E, 1), dtype=t.int64, device=self.dev)
+        kind = t.zeros(max(E, 1), dtype=t.uint8, device=self.dev)
+        counts = t.zeros((n, 4), dtype=t.int32, device=self.dev)
+        if n and V:
+            tv = t.from_numpy(v).to(self.dev)
+            self._ready()
+            self.ctx.remote_lfa_device(pcost_all.data_ptr(), tv.data_ptr(), n, i32[0].data_ptr(),
+                                       i32[1].data_ptr(), i32[2].data_ptr(), tcost.data_ptr(),
+                                       kind.data_ptr(), counts.data_ptr(), timing=timing)
+            self.ctx.synchronize()
+        h = i32[:, :E].cpu().numpy()
+        return (h[0].copy(), h[1].copy(), h[2].copy(), tcost[:E].cpu().numpy().view(np.uint64),
+                kind[:E].cpu().numpy(), counts.cpu().numpy().view(np.uint32))
 
     def frr_link_loads(self, export, nh, backup, dsts, rows, srcs, weights=None, scenarios=(),
                        planes=True, timing=False, table_budget=None):

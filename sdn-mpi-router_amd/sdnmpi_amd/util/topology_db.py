@@ -27,7 +27,8 @@ first route query raises (``sdnmpi_amd._native.NativeUnavailable`` /
 import numpy as np
 
 from ..engine import (COST_INF, COST_MAX, DEFAULT_TABLE_BUDGET, FAIR_MULT_LIMIT, INT32, LFA_MAX_V, UTIL_MAX, RouteEngine, TableCache, _gather,
-                      _host, _take, _torch, _u16, check_link_costs, least_cost_paths_lex,
+                      _edge_keys_host, _host, _take, _torch, _u16, check_link_costs,
+                      least_cost_paths_lex,
                       peak_utilisation,
                       shortest_paths_lex, tree_path)
 from ..graph import TrackedDict, Versions, export_graph, update_export
@@ -1788,6 +1789,76 @@ class TopologyDB(object):
         keys, n = np.unique(ss.astype(np.int64) * V + nh[dd, ss], return_counts=True)
         dpids = ex.csr.dpids
         return {(int(dpids[q // V]), int(dpids[q % V])): int(c) for q, c in zip(keys, n)}
+
+    # -- remote loop-free alternates (PQ-node repair tunnels) ----------------
+    def _remote_lfa_rows(self, ex):
+        """(pq, via, via_port, tunnel_cost, kind [E], counts [V, 4]) of every
+        link, on the host, kept in the least-cost memo beside the LFA tables
+        and dropped with them; :meth:`_lfa_rows`' ValueErrors."""
+        self._lfa_rows(ex, node_protect=False)      # the checks, the all-pairs table
+        m = self._cost_memo
+        if "rlfa" not in m:
+            m["rlfa"] = tuple(self.engine.remote_lfa(ex, self._cost_vector(ex), m["pall"][0]))
+        return m["rlfa"]
+
+    def remote_lfa_tables(self):
+        """Remote loop-free alternates (RFC 7490) under the link costs
+        (remote_lfa.hip), one repair per directed link e = (src -> dst): dict(pq
+        -- the PQ node the packet is tunnelled to --, via -- the neighbour it
+        leaves through --, via_port int32 [E], -1 where the link has no repair;
+        tunnel_cost uint64 [E] -- the cost src -> via -> pq --; kind uint8 [E]
+        with bits 1 = a repair exists, 2 = pq is in src's own P-space (an
+        ordinary tunnel reaches it), 4 = pq is via itself (a per-link
+        loop-free alternate, no tunnel); src, dst int32 [E] dense; dpids).
+        Needs the all-pairs least-cost table as :meth:`lfa_tables` does (the
+        same ValueErrors)."""
+        ex = self.graph()
+        pq, via, vp, tc, k, _ = self._remote_lfa_rows(ex)
+        csr = ex.csr
+        src = np.repeat(np.arange(int(csr.V), dtype=np.int32), np.diff(csr.row_ptr))
+        return {"pq": pq, "via": via, "via_port": vp, "tunnel_cost": tc, "kind": k, "src": src,
+                "dst": np.asarray(csr.col, np.int32), "dpids": csr.dpids}
+
+    def repair_tunnels(self):
+        """{(src_dpid, dst_dpid): (pq_dpid, via_dpid, via_port, tunnel_cost,
+        kind)} of every link with a repair (:meth:`remote_lfa_tables`)."""
+        t = self.remote_lfa_tables()
+        d = t["dpids"]
+        return {(int(d[t["src"][e]]), int(d[t["dst"][e]])):
+                (int(d[t["pq"][e]]), int(d[t["via"][e]]), int(t["via_port"][e]),
+                 int(t["tunnel_cost"][e]), int(t["kind"][e]))
+                for e in np.nonzero(t["kind"] & 1)[0].tolist()}
+
+    def remote_lfa_coverage(self):
+        """What remote LFA adds to ``lfa_coverage(node_protect=False)``:
+        dict(primaries, backups -- as there --, remote_backups -- the primaries
+        without a loop-free alternate whose primary link has a repair --,
+        coverage_with_remote = (backups + remote_backups) / primaries (0.0
+        without primaries), links -- the links that are no self-loops --,
+        links_repaired, links_plain -- those whose PQ node needs no directed
+        forwarding)."""
+        ex = self.graph()
+        V = int(ex.csr.V)
+        _, _, _, _, k, counts = self._remote_lfa_rows(ex)
+        lk = _host(self._lfa_rows(ex, node_protect=False)[2])
+        cov = self.lfa_coverage(node_protect=False)
+        nh = _host(self._cost_memo["pall"][1])
+        dd, ss = np.nonzero((nh >= 0) & ((lk & 1) == 0))
+        keys, _ = _edge_keys_host(ex.csr)
+        e = np.searchsorted(keys, ss.astype(np.int64) * V + nh[dd, ss])
+        remote = int((k[e] & 1).sum()) if e.size else 0
+        tot = counts.astype(np.int64).sum(axis=0)
+        prim = cov["primaries"]
+        return {"primaries": prim, "backups": cov["backups"], "remote_backups": remote,
+                "coverage_with_remote": float(cov["backups"] + remote) / prim if prim else 0.0,
+                "links": int(tot[0]), "links_repaired": int(tot[1]), "links_plain": int(tot[2])}
+
+    def unrepaired_links(self):
+        """:meth:`unprotected_links` restricted to the links without a remote
+        repair either: the cables neither a loop-free alternate nor a PQ-node
+        tunnel covers."""
+        fixed = self.repair_tunnels()
+        return {key: c for key, c in self.unprotected_links().items() if key not in fixed}
 
     def _switch_pair_cost_loads(self, ex, sv, dv, w):
         """(load uint64 [E], reach bool [n]) of switch pairs (dense ids sv ->
